@@ -28,9 +28,13 @@ bucket (ShardedTrainStep).  value = total pairs / max-over-ranks time.  The
 index line at N>1 is configs[3] candidate-sharded (ShardedBruteForceIndex,
 all_to_all of per-shard top-k lists to each query block's owner + merge).
 
-The JSON line also carries the roofline of the dominant kernel (the fused
-in-batch rows pass, bf16 MFMA), the index QPS of BASELINE configs[3] at a
-bounded query count on this GPU, and the CPU baseline (oracle/ numpy fp32
+A plain run (`--gpus 1 --steps N --warmup W`) does only that: set up, warm
+up, time the N steps, print the line (value, ms_per_step, final_loss).
+`--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs).  With `--full` the JSON line also carries the roofline of the
+dominant kernel (the fused in-batch rows pass, bf16 MFMA), the gather's, the
+index QPS of BASELINE configs[3] at a bounded query count on this GPU, the C5
+table and input-pipeline legs, and the CPU baseline (oracle/ numpy fp32
 restatement of the same step on a bounded sample).
 """
 from __future__ import annotations
@@ -223,7 +227,38 @@ def time_train(args, model, data, device, ws):
     if getattr(step, "host_times", None):
         print("host ms/step by phase:", {k: round(v / args.steps * 1e3, 3)
                                          for k, v in step.host_times.items()}, file=sys.stderr)  # timed steps only
-    return dt, loss
+    return dt, loss, out
+
+
+DUMP_ROWS = 8192  # rows of a large table written by --dump-outputs (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir: str, out, model, sharded: bool) -> None:
+    """--dump-outputs: what the last timed step handed its caller, one
+    <name>.npy each (float64 loss, float32 parameters, a few tens of MB in all):
+    the returned `loss`, and the state the step left in the model it trains in
+    place — every dense layer's weight and bias and every embedding table
+    (tables over DUMP_ROWS rows as a fixed seeded sample of their rows, sorted).
+    Batches, initial weights and the sample are seeded, so two builds run with
+    the same arguments write comparable arrays.  The row-sharded step holds
+    the large tables itself: its dump is the loss and the dense layers."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": out["loss"].detach().double().reshape(1).cpu().numpy()}
+    rng = np.random.default_rng(4321)
+    for side, tower in (("query", model.query_tower), ("candidate", model.candidate_tower)):
+        for li, (w, b) in enumerate(tower.dense.params()):
+            arrays[f"{side}_dense{li}_weight"] = w.detach().float().cpu().numpy()
+            arrays[f"{side}_dense{li}_bias"] = b.detach().float().cpu().numpy()
+        if sharded:
+            continue
+        for name, layer in tower.input_layer.embedding_layers.items():
+            w = layer.weight.detach()
+            if w.shape[0] > DUMP_ROWS:
+                rows = np.sort(rng.choice(w.shape[0], DUMP_ROWS, replace=False))
+                w = w[torch.as_tensor(rows, device=w.device)]
+            arrays[f"{side}_table_{name}"] = w.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def local_batch(args, ws: int) -> int:
@@ -949,12 +984,67 @@ def cpu_baseline(seconds_budget: float = 20.0):
                       f"restatement oracle/oracle.py:CpuTwoTower, {t_total:.1f}s"}
 
 
+def full_legs(result, args, model, data, device, ws, rank, inbatch, gather):
+    """--full: the legs beside the train-step line, added to `result` — the
+    in-batch kernels' roofline and the gather's (both timed before the train
+    step, handed in), then index, C5 table, input pipeline and CPU baseline."""
+    B, value = args.batch, result["value"]
+    flops, ms_rows, ms_cols, ms_entry, ms_x3 = inbatch
+    (ms_rows, ms_rows_1), (ms_cols, ms_cols_1) = ms_rows, ms_cols
+    achieved = flops / (ms_rows * 1e-3) / 1e12
+    result["roofline"] = {
+        "kernel": "inbatch_pass_kernel<128,0> (rows pass of tt_inbatch_softmax_xent: S=QC^T-logq, online "
+                  "softmax, P.C), HIP events on its launch stream around 10 back-to-back launches "
+                  "(tt_probe_arm_repeat), 4 samples",
+        "bound": "mfma",
+        "achieved": achieved,
+        "peak": MI355X_BF16_DENSE_TFLOPS,
+        "unit": "TFLOP/s",
+        "frac": achieved / MI355X_BF16_DENSE_TFLOPS,
+        "traffic": (pmc_traffic("inbatch_pass_kernel<128, 0>") or {}).get("bytes_per_launch"),
+        "traffic_source": (pmc_traffic("inbatch_pass_kernel<128, 0>") or {}).get("source"),
+        "ms_per_launch": ms_rows,
+        "ms_per_launch_one_event_pair_each": ms_rows_1,
+        "cols_pass": {"kernel": "inbatch_pass_kernel<128,1>", "ms_per_launch": ms_cols,
+                      "ms_per_launch_one_event_pair_each": ms_cols_1,
+                      "achieved": flops / (ms_cols * 1e-3) / 1e12},
+        "ms_fused_entry": ms_entry,
+        "ms_fused_entry_x3": ms_x3,
+        "algorithmic_flops_per_launch": flops,
+    }
+    result["gather_roofline"] = gather
+    rp = rocprof_avg_ms("inbatch_pass_kernel<128, 0>")
+    if rp is not None:
+        # the profiler's dispatch timestamps (no event overhead around each launch)
+        a_rp = flops / (rp["ms"] * 1e-3) / 1e12
+        result["roofline"]["rocprof"] = {"ms_per_launch": rp["ms"], "calls": rp["calls"], "achieved": a_rp,
+                                         "frac": a_rp / MI355X_BF16_DENSE_TFLOPS, "source": rp["source"]}
+    if ws == 1 and args.index_mode == "auto" and not args.no_index:
+        result["index"] = time_index(device, args.index_queries, HM_VOCAB["article_id"], 100)
+        result["index"]["runner_recall_e2e"] = time_runner_recall(model, data, device)
+    elif not args.no_index:
+        result["index"] = time_index_sharded(device, args.index_queries, HM_VOCAB["article_id"], 100, ws, rank)
+    if not args.no_c5:
+        result["c5_sharded_table"] = time_c5_sharded(device, ws, rank)
+    if ws == 1 and args.pipeline_rows > 0:
+        result["pipeline"] = time_pipeline(model, data, device, args.pipeline_rows, B)
+        result["pipeline"]["vs_train_step_rate"] = result["pipeline"]["rows_per_s"] / value
+    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=16384)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the train-step line: kernel rooflines, gather, index, C5, pipeline and CPU-baseline "
+                         "legs (which --index-queries, --no-index, --index-mode, --no-uniform-gather, --pipeline-rows, "
+                         "--no-cpu-baseline, --cpu-seconds, --no-c5 and --c5-only choose among)")
     ap.add_argument("--index-queries", type=int, default=1_000_000)
     ap.add_argument("--no-index", action="store_true")
     ap.add_argument("--fused-apply", action="store_true",
@@ -975,6 +1065,8 @@ def main():
     ap.add_argument("--index-mode", choices=("auto", "sharded"), default="auto",
                     help="sharded: run the N>1 candidate-sharded index (search_owned) even on one rank")
     args = ap.parse_args()
+    if args.c5_only and not args.full:
+        ap.error("--c5-only is a leg of the full benchmark: add --full")
 
     # stdout carries exactly one JSON line: everything else written to fd 1
     # (RCCL's version banner, library chatter) goes to stderr
@@ -1012,19 +1104,20 @@ def main():
 
     model, data = build_model(device, rank, args.fused_apply)
     B = args.batch
-    # kernel-level timings on the unsharded model, before the train step takes its tables
-    flops, ms_rows, ms_cols, ms_entry, ms_x3 = time_inbatch_kernel(model, data, device, B)
-    gather = time_gather(model, data, device, B)
-    if ws == 1 and not args.no_uniform_gather:
-        gather["uniform_ids"] = time_gather_uniform(model, device, B)
-    dt, loss = time_train(args, model, data, device, ws)
+    if args.full:
+        # kernel-level timings on the unsharded model, before the train step takes its tables
+        inbatch = time_inbatch_kernel(model, data, device, B)
+        gather = time_gather(model, data, device, B)
+        if ws == 1 and not args.no_uniform_gather:
+            gather["uniform_ids"] = time_gather_uniform(model, device, B)
+    dt, loss, out = time_train(args, model, data, device, ws)
     global_neg = ws > 1 and args.negatives == "global"
     pairs = (B if global_neg else ws * B) * args.steps
     value = pairs / dt
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model, sharded=ws > 1 or args.train_mode == "sharded")
 
-    (ms_rows, ms_rows_1), (ms_cols, ms_cols_1) = ms_rows, ms_cols
-    achieved = flops / (ms_rows * 1e-3) / 1e12
     result = {
         "metric": "positive pairs/sec (train) + index QPS @ Recall@100, 1/2/4/8 MI355X",
         "value": value,
@@ -1050,49 +1143,11 @@ def main():
             "parallelism": f"dp{ws}",
         },
         "final_loss": loss,
-        "roofline": {
-            "kernel": "inbatch_pass_kernel<128,0> (rows pass of tt_inbatch_softmax_xent: S=QC^T-logq, online "
-                      "softmax, P.C), HIP events on its launch stream around 10 back-to-back launches "
-                      "(tt_probe_arm_repeat), 4 samples",
-            "bound": "mfma",
-            "achieved": achieved,
-            "peak": MI355X_BF16_DENSE_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": achieved / MI355X_BF16_DENSE_TFLOPS,
-            "traffic": (pmc_traffic("inbatch_pass_kernel<128, 0>") or {}).get("bytes_per_launch"),
-            "traffic_source": (pmc_traffic("inbatch_pass_kernel<128, 0>") or {}).get("source"),
-            "ms_per_launch": ms_rows,
-            "ms_per_launch_one_event_pair_each": ms_rows_1,
-            "cols_pass": {"kernel": "inbatch_pass_kernel<128,1>", "ms_per_launch": ms_cols,
-                          "ms_per_launch_one_event_pair_each": ms_cols_1,
-                          "achieved": flops / (ms_cols * 1e-3) / 1e12},
-            "ms_fused_entry": ms_entry,
-            "ms_fused_entry_x3": ms_x3,
-            "algorithmic_flops_per_launch": flops,
-        },
-        "gather_roofline": gather,
     }
     if rehearse:
         result["rehearsal"] = "TT_BENCH_REHEARSE: ranks share GPUs over gloo; not a measurement"
-
-    rp = rocprof_avg_ms("inbatch_pass_kernel<128, 0>")
-    if rp is not None:
-        # the profiler's dispatch timestamps (no event overhead around each launch)
-        a_rp = flops / (rp["ms"] * 1e-3) / 1e12
-        result["roofline"]["rocprof"] = {"ms_per_launch": rp["ms"], "calls": rp["calls"], "achieved": a_rp,
-                                         "frac": a_rp / MI355X_BF16_DENSE_TFLOPS, "source": rp["source"]}
-    if ws == 1 and args.index_mode == "auto" and not args.no_index:
-        result["index"] = time_index(device, args.index_queries, HM_VOCAB["article_id"], 100)
-        result["index"]["runner_recall_e2e"] = time_runner_recall(model, data, device)
-    elif not args.no_index:
-        result["index"] = time_index_sharded(device, args.index_queries, HM_VOCAB["article_id"], 100, ws, rank)
-    if not args.no_c5:
-        result["c5_sharded_table"] = time_c5_sharded(device, ws, rank)
-    if ws == 1 and args.pipeline_rows > 0:
-        result["pipeline"] = time_pipeline(model, data, device, args.pipeline_rows, B)
-        result["pipeline"]["vs_train_step_rate"] = result["pipeline"]["rows_per_s"] / value
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+    if args.full:
+        full_legs(result, args, model, data, device, ws, rank, inbatch, gather)
     if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(result) + "\n").encode())

@@ -117,6 +117,43 @@ def test_main_schema_widths_match_survey():
     assert InputLayer(s.candidate_features, device=torch.device("cpu")).output_dim == 200
 
 
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array; a table
+    over DUMP_ROWS rows is written as the same sorted row sample every time,
+    smaller ones whole; the row-sharded step's dump has no tables."""
+    from types import SimpleNamespace as NS
+
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(bench.DUMP_ROWS + 1000, 4, generator=g)
+    small = torch.randn(5, 2, generator=g)
+
+    def tower(tables):
+        dense = NS(params=lambda: [(torch.randn(3, 2, generator=g), torch.zeros(2))])
+        return NS(dense=dense, input_layer=NS(embedding_layers={k: NS(weight=v) for k, v in tables.items()}))
+
+    model = NS(query_tower=tower({"big": big}), candidate_tower=tower({"small": small}))
+    out = {"loss": torch.tensor(1.5)}
+    bench.dump_outputs(str(tmp_path / "a"), out, model, sharded=False)
+    bench.dump_outputs(str(tmp_path / "b"), out, model, sharded=False)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("loss", "query_dense0_weight", "query_dense0_bias", "query_table_big",
+                                                "candidate_dense0_weight", "candidate_dense0_bias",
+                                                "candidate_table_small"))
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["loss.npy"].tolist() == [1.5]
+    assert np.array_equal(a["candidate_table_small.npy"], small.numpy())
+    assert a["query_table_big.npy"].shape == (bench.DUMP_ROWS, 4)
+    assert np.array_equal(a["query_table_big.npy"], np.load(tmp_path / "b" / "query_table_big.npy"))
+    # the sample is rows of the table, in ascending row order
+    rows = [int(np.flatnonzero((big.numpy() == r).all(axis=1))[0]) for r in a["query_table_big.npy"][:64]]
+    assert rows == sorted(rows) and len(set(rows)) == 64
+    bench.dump_outputs(str(tmp_path / "s"), out, model, sharded=True)
+    assert not [n for n in os.listdir(tmp_path / "s") if "_table_" in n]
+
+
 def test_static_index_recall_golden_host_path():
     g = GOLD["recall"]
     feats = [Feature("query_id", dtypes.string, FeatureFamily.QUERY, embedding_size=2)]
