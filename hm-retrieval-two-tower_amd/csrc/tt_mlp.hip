@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "tt_common.h"
 #include "tt_mlp_pack.h"
@@ -560,6 +561,257 @@ __global__ void __launch_bounds__(kWgThreads) mlp_wgrad_pair_kernel(const WgradA
   else mlp_wgrad_block<MASK>(a1, b - split, wsm);
 }
 
+// The wide-tile form of the same product (the default; TT_WGRAD_TILE=64 keeps
+// the kernel above as the reference path).  One workgroup owns a
+// 64 WI x 64 WJ output tile (128 x 64, 64 x 128 or 128 x 128; wgrad_tile()
+// below picks, DESIGN section 9 has what each measured), wave w the quadrant
+// (w & 1, w >> 1) of it: WI x WJ MFMA blocks, so per k-step a wave reads
+// WI + WJ fragments per plane and issues 3 WI WJ MFMAs (12 per 16 transposing
+// reads, where the 64 x 64 tile issues 3 per 8), each A element is re-read and
+// split by N / (64 WJ) column tiles instead of N / 64 and each G element by
+// (Ka + 1) / (64 WI) row tiles.  The splits, the 16-row k-steps from the
+// split's first row, the k -> lane mapping of the fragments and the order of
+// the three products are those of the 64 x 64 kernel, so every output element
+// sums the same terms in the same order: the two are bit-identical.
+// Stage: 32 rows, planes A hi, A lo, G hi, G lo; a 128-column plane has rows
+// 320 B apart (256 B of data), a 64-column one 192 B.  Banks: a transposing
+// read serves a 32-lane half per cycle over 64 banks; its 4 rows x 2 16-lane
+// groups are 8 banks wide each and start at bank 80 q + 8 g = 16 q + 8 g
+// (mod 64) for the 320-B pitch (48 q + 8 g for 192 B) past the fragment's
+// first column: eight disjoint ranges that cover the 64 banks.  The stash
+// stores 16 B per lane with the 16 (8) lanes of a row writing its 256 (128)
+// contiguous bytes: every 8-lane group of a ds_write_b128 covers the 32 store
+// banks once.  128 x 128: 40 KiB per stage, 80 KiB double-buffered (64 KiB for
+// the two half-wide shapes), and at most 256 registers (2 waves per SIMD), so
+// two workgroups share a CU — the two towers' launches run side by side.  Two
+// stages of loads are in flight (three do not fit the registers beside the
+// accumulators: the 128 x 128 build spilled ~100 registers).  The splits are
+// not the tile's to change, so a wide tile has 2-4 x fewer workgroups (96-256
+// at the C3 shapes, one per CU at most): what it saves in staged bytes and
+// conversions it partly pays back in exposed load latency.
+constexpr int wg_pitch(int w) { return w == 2 ? 320 : 192; }
+typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned wg_pack2(float lo, float hi) {  // bf16(lo) | bf16(hi) << 16
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{lo, hi}, wg_bf16x2));
+}
+template <int WI, int WJ>
+constexpr int kWgWideStageB = 2 * kWgBK * (wg_pitch(WI) + wg_pitch(WJ));
+
+template <bool MASK, int WI, int WJ>
+__device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const int b, char* wsm) {
+  constexpr int TA = 64 * WI, TG = 64 * WJ;
+  constexpr int PA = wg_pitch(WI), PG = wg_pitch(WJ);
+  constexpr int PLA = kWgBK * PA, PLG = kWgBK * PG;  // plane bytes
+  constexpr int STAGE = kWgWideStageB<WI, WJ>;
+  constexpr int RA = kWgBK / WI, RG = kWgBK / WJ;  // rows per loader pass
+  constexpr int D = 2;                             // stages of global loads in flight
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int lane = lane_id();
+  // b -> (split, tile) as in mlp_wgrad_block
+  const int tiles = a.TI * a.TJ;
+  int split, tile;
+  if (a.S % 8 == 0) {
+    const int q = b >> 3;
+    tile = q % tiles;
+    split = (q / tiles) * 8 + (b & 7);
+  } else {
+    tile = b % tiles;
+    split = b / tiles;
+  }
+  const int i0 = (tile / a.TJ) * TA;
+  const int j0 = (tile % a.TJ) * TG;
+  const int64_t r0 = static_cast<int64_t>(split) * a.rows_per_split;
+  int64_t r1 = r0 + a.rows_per_split;
+  if (r1 > a.M) r1 = a.M;
+  if (r1 < r0) r1 = r0;  // an empty split: 0-byte descriptors, every load reads 0
+  const int nstage = r1 > r0 ? static_cast<int>((r1 - r0 + kWgBK - 1) / kWgBK) : 0;
+  const float s = a.scale ? *a.scale : 1.0f;
+
+  // loader: an operand tile of 64 W columns has 8 W lanes per row (8 columns
+  // each) and is staged in W passes of 32 / W rows
+  const int rowa = tid / (8 * WI), cola = (tid % (8 * WI)) * 8;
+  const int rowg = tid / (8 * WJ), colg = (tid % (8 * WJ)) * 8;
+  const __amdgpu_buffer_rsrc_t dA = mlp_desc(a.A + r0 * a.lda, static_cast<uint64_t>(r1 - r0) * a.lda * 4);
+  const __amdgpu_buffer_rsrc_t dG = mlp_desc(a.G + r0 * a.ldg, static_cast<uint64_t>(r1 - r0) * a.ldg * 4);
+  const __amdgpu_buffer_rsrc_t dM =
+      mlp_desc(MASK ? a.gmask + r0 * a.ldgm : a.G, static_cast<uint64_t>(r1 - r0) * (MASK ? a.ldgm : a.ldg) * 4);
+  const unsigned lda4 = static_cast<unsigned>(a.lda) * 4, ldg4 = static_cast<unsigned>(a.ldg) * 4,
+                 ldm4 = static_cast<unsigned>(MASK ? a.ldgm : a.ldg) * 4;
+  const int ca = i0 + cola, cg = j0 + colg;
+  const unsigned oa = rowa * lda4 + static_cast<unsigned>(ca) * 4;
+  const unsigned og = rowg * ldg4 + static_cast<unsigned>(cg) * 4;
+  const unsigned om = rowg * ldm4 + static_cast<unsigned>(cg) * 4;
+  f32x4 va[D][WI][2], vg[D][WJ][2], vm[D][MASK ? WJ : 1][2];
+  auto fetch = [&](int st, auto slot_c) {
+    constexpr int SL = decltype(slot_c)::value;
+#pragma unroll
+    for (int p = 0; p < WI; ++p) {
+      const unsigned sa = static_cast<unsigned>(st * kWgBK + p * RA) * lda4;
+      va[SL][p][0] = mlp_load4s(dA, oa, sa);
+      va[SL][p][1] = mlp_load4s(dA, oa + 16, sa);
+    }
+#pragma unroll
+    for (int p = 0; p < WJ; ++p) {
+      const unsigned sg = static_cast<unsigned>(st * kWgBK + p * RG) * ldg4;
+      vg[SL][p][0] = mlp_load4s(dG, og, sg);
+      vg[SL][p][1] = mlp_load4s(dG, og + 16, sg);
+      if constexpr (MASK) {
+        const unsigned sm = static_cast<unsigned>(st * kWgBK + p * RG) * ldm4;
+        vm[SL][p][0] = mlp_load4s(dM, om, sm);
+        vm[SL][p][1] = mlp_load4s(dM, om + 16, sm);
+      }
+    }
+  };
+  // 8 values -> 16 B of hi at p and 16 B of lo one plane on; two values per
+  // conversion (v_cvt_pk_bf16_f32: the rounding of bf16_bits)
+  auto put8 = [&](char* p, int plane, const float (&x)[8]) {
+    unsigned hw[4], lw[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      hw[e] = wg_pack2(x[2 * e], x[2 * e + 1]);
+      lw[e] = wg_pack2(x[2 * e] - __uint_as_float(hw[e] << 16), x[2 * e + 1] - __uint_as_float(hw[e] & 0xffff0000u));
+    }
+    *reinterpret_cast<u32x4*>(p) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+    *reinterpret_cast<u32x4*>(p + plane) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+  };
+  // EDGE: the tile reaches past column Ka - 1 of A (the ones column, padding)
+  // or past column N - 1 of Gm; an interior tile stages what it loaded
+  auto stash = [&](int st, int buf, auto slot_c, auto edge_c) {
+    constexpr int SL = decltype(slot_c)::value;
+    constexpr bool EDGE = decltype(edge_c)::value;
+    char* base = wsm + buf * STAGE;
+    float x[8];
+#pragma unroll
+    for (int p = 0; p < WI; ++p) {
+      const int row = rowa + p * RA;
+      const bool live = EDGE && r0 + static_cast<int64_t>(st) * kWgBK + row < r1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {  // [A | 1]: the ones column is the bias row of the output
+        const int col = ca + e;
+        const float v = va[SL][p][e >> 2][e & 3];
+        x[e] = !EDGE || col < a.Ka ? v : ((col == a.Ka && live) ? 1.0f : 0.0f);
+      }
+      put8(base + row * PA + cola * 2, PLA, x);
+    }
+#pragma unroll
+    for (int p = 0; p < WJ; ++p) {
+      const int row = rowg + p * RG;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int col = cg + e;
+        float v = !EDGE || col < a.N ? vg[SL][p][e >> 2][e & 3] : 0.0f;
+        if constexpr (MASK) v = vm[SL][p][e >> 2][e & 3] > 0.0f ? v * s : 0.0f;
+        x[e] = v;
+      }
+      put8(base + 2 * PLA + row * PG + colg * 2, PLG, x);
+    }
+  };
+
+  // fragments as in mlp_wgrad_block: 16-lane group g -> rows / columns
+  // 16 (g & 1) .. + 15 of a 32-block, batch rows 8 (g >> 1) .. + 7 of the k-step
+  const int ib = wave & 1, jb = wave >> 1;
+  const int g = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
+  const int frow = 8 * (g >> 1) + q;
+  const int fa = frow * PA + (32 * WI * ib + 16 * (g & 1) + 4 * p4) * 2;
+  const int fg = 2 * PLA + frow * PG + (32 * WJ * jb + 16 * (g & 1) + 4 * p4) * 2;
+  auto frag = [&](const char* at, int pitch) {
+    const wg_bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(at));
+    const wg_bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(at + 4 * pitch));
+    return __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  f32x16 acc[WI][WJ] = {};
+  auto compute = [&](int buf) {
+    const char* base = wsm + buf * STAGE;
+#pragma unroll
+    for (int ks = 0; ks < kWgBK / 16; ++ks) {
+      bf16x8 ah[WI], al[WI], gh[WJ], gl[WJ];
+#pragma unroll
+      for (int bi = 0; bi < WI; ++bi) {
+        ah[bi] = frag(base + fa + ks * 16 * PA + bi * 64, PA);
+        al[bi] = frag(base + PLA + fa + ks * 16 * PA + bi * 64, PA);
+      }
+#pragma unroll
+      for (int bj = 0; bj < WJ; ++bj) {
+        gh[bj] = frag(base + fg + ks * 16 * PG + bj * 64, PG);
+        gl[bj] = frag(base + PLG + fg + ks * 16 * PG + bj * 64, PG);
+      }
+#pragma unroll
+      for (int bi = 0; bi < WI; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < WJ; ++bj) {
+          acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[bi], gh[bj], acc[bi][bj], 0, 0, 0);
+          acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], gl[bj], acc[bi][bj], 0, 0, 0);
+          acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], gh[bj], acc[bi][bj], 0, 0, 0);
+        }
+    }
+  };
+
+  // pipeline: stage st + 1 is split and stashed into the other buffer in the
+  // same scheduling region as the MFMAs of stage st, so one wave's conversions
+  // run under its own MFMAs (with one or two waves per SIMD nothing else
+  // would); one barrier per stage: past it every wave has computed stage st
+  // (its buffer is free for stage st + 2) and stashed stage st + 1.  Stage X
+  // is fetched into slot X & 1 two steps before it is stashed.
+  auto pipeline = [&](auto edge_c) {
+    fetch(0, std::integral_constant<int, 0>());
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(1, std::integral_constant<int, 1>());
+    __builtin_amdgcn_sched_barrier(0);
+    stash(0, 0, std::integral_constant<int, 0>(), edge_c);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(2, std::integral_constant<int, 0>());
+    __builtin_amdgcn_sched_barrier(0);
+    lds_barrier();
+    auto step = [&](int st, auto slot_c) {  // slot_c: the slot of stage st + 1
+      __builtin_amdgcn_sched_barrier(0);
+      compute(st & 1);
+      stash(st + 1, (st + 1) & 1, slot_c, edge_c);  // past the split: zeros, unused
+      __builtin_amdgcn_sched_barrier(0);
+      fetch(st + 1 + D, slot_c);
+      __builtin_amdgcn_sched_barrier(0);
+      lds_barrier();
+    };
+    for (int st = 0; st < nstage; st += 2) {
+      step(st, std::integral_constant<int, 1>());
+      step(st + 1, std::integral_constant<int, 0>());
+    }
+  };
+  // workgroup-uniform: a scalar branch, every lane stays active for the transposing reads
+  if (i0 + TA > a.Ka || j0 + TG > a.N) pipeline(std::true_type());
+  else pipeline(std::false_type());
+
+  const int rows_out = a.Ka + 1;
+  float* P = a.parts + static_cast<int64_t>(split) * rows_out * a.N;
+#pragma unroll
+  for (int bi = 0; bi < WI; ++bi)
+#pragma unroll
+    for (int bj = 0; bj < WJ; ++bj) {
+      const int n = j0 + 32 * (WJ * jb + bj) + (lane & 31);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = i0 + 32 * (WI * ib + bi) + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (n < a.N && row < rows_out) P[static_cast<int64_t>(row) * a.N + n] = acc[bi][bj][r];
+      }
+    }
+}
+
+template <bool MASK, int WI, int WJ>
+__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_wide_kernel(const WgradArgs a) {
+  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgWideStageB<WI, WJ>];
+  mlp_wgrad_wide_block<MASK, WI, WJ>(a, blockIdx.x, wsm);
+}
+
+template <bool MASK, int WI, int WJ>
+__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_wide_pair_kernel(const WgradArgs a0, const WgradArgs a1,
+                                                                            const int split) {
+  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgWideStageB<WI, WJ>];
+  const int b = blockIdx.x;
+  if (b < split) mlp_wgrad_wide_block<MASK, WI, WJ>(a0, b, wsm);
+  else mlp_wgrad_wide_block<MASK, WI, WJ>(a1, b - split, wsm);
+}
+
 // out[e] = sum over splits of parts[sp][e] (deterministic): a block covers 64
 // float4 of the output; group g of 16 adds splits [g S/16, (g+1) S/16) in
 // order (their loads all in flight), then the 16 group sums are added in
@@ -832,10 +1084,31 @@ extern "C" size_t tt_mlp_wgrad_workspace_size(int64_t M, int32_t Ka, int32_t N) 
   return static_cast<size_t>(wgrad_splits(M, Ka, N)) * (Ka + 1) * N * sizeof(float);
 }
 
+// The output tile of the weight-gradient launches, in 64-wide units per side
+// ([A | 1] columns x Gm columns).  TT_WGRAD_TILE (read at every call, so one
+// process can run every form): unset = the wide kernel, 128 x 64 for a masked
+// problem (Gm and its mask are the doubled stream: half as many row tiles
+// re-read them) and 64 x 128 otherwise; 128 = 128 x 128; 128x64 / 64x128 =
+// that shape for every problem; 64 = the 64 x 64 reference kernel.
+struct WgradTile {
+  int wi, wj;
+};
+static WgradTile wgrad_tile(bool masked) {
+  const char* e = std::getenv("TT_WGRAD_TILE");
+  if (!e || !*e) return masked ? WgradTile{2, 1} : WgradTile{1, 2};
+  if (!std::strcmp(e, "128")) return {2, 2};
+  if (!std::strcmp(e, "64")) return {1, 1};
+  if (!std::strcmp(e, "128x64")) return {2, 1};
+  if (!std::strcmp(e, "64x128")) return {1, 2};
+  return {0, 0};
+}
+#define TT_REQUIRE_WGRAD_TILE(t, fn) \
+  TT_REQUIRE((t).wi != 0, "%s: TT_WGRAD_TILE must be 128, 64, 128x64 or 64x128", fn)
+
 // Validates one tt_mlp_wgrad problem into its kernel arguments (parts unset).
 static int wgrad_setup(const char* fn, const float* A, int64_t lda, const float* G, int64_t ldg, const float* gmask,
                        int64_t ldgm, const float* scale, int64_t M, int32_t Ka, int32_t N, float* dwb,
-                       WgradArgs& a) {
+                       const WgradTile t, WgradArgs& a) {
   TT_REQUIRE(dwb && (M == 0 || (A && G)), "%s: NULL A/G/dwb", fn);
   TT_REQUIRE(M >= 0 && Ka >= 1 && Ka <= 4096, "%s: Ka=%d outside [1, 4096]", fn, Ka);
   TT_REQUIRE(N >= 4 && N <= 4096 && N % 4 == 0, "%s: N=%d must be a multiple of 4 in [4, 4096]", fn, N);
@@ -861,17 +1134,33 @@ static int wgrad_setup(const char* fn, const float* A, int64_t lda, const float*
   a.M = M;
   a.Ka = Ka;
   a.N = N;
-  a.TI = static_cast<int>(ceil_div(Ka + 1, kWgTile));
-  a.TJ = static_cast<int>(ceil_div(N, kWgTile));
+  a.TI = static_cast<int>(ceil_div(Ka + 1, kWgTile * t.wi));
+  a.TJ = static_cast<int>(ceil_div(N, kWgTile * t.wj));
   a.S = S;
   a.rows_per_split = rps;
   return TT_OK;
 }
 
-static void launch_wgrad(const WgradArgs& a, hipStream_t st) {
+template <int WI, int WJ>
+static void launch_wgrad_wide(const WgradArgs& a, dim3 grid, hipStream_t st) {
+  if (a.gmask) hipLaunchKernelGGL((mlp_wgrad_wide_kernel<true, WI, WJ>), grid, dim3(kWgThreads), 0, st, a);
+  else hipLaunchKernelGGL((mlp_wgrad_wide_kernel<false, WI, WJ>), grid, dim3(kWgThreads), 0, st, a);
+}
+
+static void launch_wgrad(const WgradArgs& a, const WgradTile t, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(a.S * a.TI * a.TJ));
-  if (a.gmask) hipLaunchKernelGGL((mlp_wgrad_kernel<true>), grid, dim3(kWgThreads), 0, st, a);
+  if (t.wi == 2 && t.wj == 2) launch_wgrad_wide<2, 2>(a, grid, st);
+  else if (t.wi == 2) launch_wgrad_wide<2, 1>(a, grid, st);
+  else if (t.wj == 2) launch_wgrad_wide<1, 2>(a, grid, st);
+  else if (a.gmask) hipLaunchKernelGGL((mlp_wgrad_kernel<true>), grid, dim3(kWgThreads), 0, st, a);
   else hipLaunchKernelGGL((mlp_wgrad_kernel<false>), grid, dim3(kWgThreads), 0, st, a);
+}
+
+template <int WI, int WJ>
+static void launch_wgrad_wide_pair(const WgradArgs& a0, const WgradArgs& a1, int nb0, dim3 grid, hipStream_t st) {
+  if (a0.gmask)
+    hipLaunchKernelGGL((mlp_wgrad_wide_pair_kernel<true, WI, WJ>), grid, dim3(kWgThreads), 0, st, a0, a1, nb0);
+  else hipLaunchKernelGGL((mlp_wgrad_wide_pair_kernel<false, WI, WJ>), grid, dim3(kWgThreads), 0, st, a0, a1, nb0);
 }
 
 namespace {
@@ -879,13 +1168,15 @@ int wgrad_one(const char* fn, const float* A, int64_t lda, const float* G, int64
               int64_t ldgm, const float* scale, int64_t M, int32_t Ka, int32_t N, float* dwb, void* workspace,
               size_t workspace_bytes, tt_stream_t stream, const PartsAdagrad& ad) {
   WgradArgs a;
-  const int rc = wgrad_setup(fn, A, lda, G, ldg, gmask, ldgm, scale, M, Ka, N, dwb, a);
+  const WgradTile t = wgrad_tile(gmask != nullptr);
+  TT_REQUIRE_WGRAD_TILE(t, fn);
+  const int rc = wgrad_setup(fn, A, lda, G, ldg, gmask, ldgm, scale, M, Ka, N, dwb, t, a);
   if (rc != TT_OK) return rc;
   TT_REQUIRE(workspace && workspace_bytes >= tt_mlp_wgrad_workspace_size(M, Ka, N), "%s: workspace %zu < %zu", fn,
              workspace_bytes, tt_mlp_wgrad_workspace_size(M, Ka, N));
   a.parts = static_cast<float*>(workspace);
   hipStream_t st = to_stream(stream);
-  launch_wgrad(a, st);
+  launch_wgrad(a, t, st);
   TT_CHECK_LAUNCH();
   const int64_t len = static_cast<int64_t>(Ka + 1) * N;
   hipLaunchKernelGGL(mlp_sum_parts_kernel, dim3(ceil_div(len, 256)), dim3(1024), 0, st, a.parts, a.S, len, dwb, ad);
@@ -929,10 +1220,13 @@ extern "C" int tt_mlp_wgrad_pair(const tt_mlp_wgrad_problem* p, void* workspace,
   clear_error();
   TT_REQUIRE(p, "tt_mlp_wgrad_pair: NULL problems");
   WgradArgs a[2];
+  WgradTile t[2];
   for (int i = 0; i < 2; ++i) {
     const tt_mlp_wgrad_problem& q = p[i];
+    t[i] = wgrad_tile(q.gmask != nullptr);
+    TT_REQUIRE_WGRAD_TILE(t[i], "tt_mlp_wgrad_pair");
     const int rc = wgrad_setup("tt_mlp_wgrad_pair", q.A, q.lda, q.G, q.ldg, q.gmask, q.ldgm, q.scale, q.M, q.Ka, q.N,
-                               q.dwb, a[i]);
+                               q.dwb, t[i], a[i]);
     if (rc != TT_OK) return rc;
   }
   const size_t need = tt_mlp_wgrad_pair_workspace_size(p);
@@ -942,11 +1236,14 @@ extern "C" int tt_mlp_wgrad_pair(const tt_mlp_wgrad_problem* p, void* workspace,
   hipStream_t st = to_stream(stream);
   const int nb0 = a[0].S * a[0].TI * a[0].TJ, nb1 = a[1].S * a[1].TI * a[1].TJ;
   if ((a[0].gmask != nullptr) != (a[1].gmask != nullptr) || nb0 % 8 != 0) {
-    launch_wgrad(a[0], st);
-    launch_wgrad(a[1], st);
-  } else {
+    launch_wgrad(a[0], t[0], st);
+    launch_wgrad(a[1], t[1], st);
+  } else {  // both masked or both not: one tile shape
     const dim3 grid(static_cast<unsigned>(nb0 + nb1));
-    if (a[0].gmask) hipLaunchKernelGGL((mlp_wgrad_pair_kernel<true>), grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
+    if (t[0].wi == 2 && t[0].wj == 2) launch_wgrad_wide_pair<2, 2>(a[0], a[1], nb0, grid, st);
+    else if (t[0].wi == 2) launch_wgrad_wide_pair<2, 1>(a[0], a[1], nb0, grid, st);
+    else if (t[0].wj == 2) launch_wgrad_wide_pair<1, 2>(a[0], a[1], nb0, grid, st);
+    else if (a[0].gmask) hipLaunchKernelGGL((mlp_wgrad_pair_kernel<true>), grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
     else hipLaunchKernelGGL((mlp_wgrad_pair_kernel<false>), grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
   }
   TT_CHECK_LAUNCH();
