@@ -229,7 +229,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // first's barrier and DMA waits.  At one per CU (the mask_diag of the
 // contract commit in its 64-bit form needed 302) the passes ran 25 % slower.
 //
-// X3 (opt-in, tt_inbatch_softmax_xent_x3): fp32-faithful products — S and
+// X3 (opt-in, tt_inbatch_softmax_xent_x3 and tt_inbatch_xent_rows_x3 /
+// _cols_x3): fp32-faithful products — S and
 // P.V both from bf16x3 products hi.hi + hi.lo + lo.hi of split operands (x =
 // hi + lo, both bf16; P split the same way in registers), three MFMAs where
 // the default issues one; the streamed rows' lo image has a ring of its own
@@ -866,16 +867,19 @@ Plan make_plan(int64_t n_stat, int64_t n_strm, int dim) {
 struct PassWs {
   __bf16* stat;
   __bf16* strm;
+  __bf16 *stat_lo, *strm_lo;  // x3 mode only
   float* bias;
   float* part_m;
   float* part_l;
   float* part_o;
 };
 
-PassWs carve_pass(Carver& cv, const Plan& p) {
+PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false) {
   PassWs w;
   w.stat = cv.take<__bf16>(p.stat_pad * p.D);
   w.strm = cv.take<__bf16>(p.strm_pad * p.D);
+  w.stat_lo = x3 ? cv.take<__bf16>(p.stat_pad * p.D) : nullptr;
+  w.strm_lo = x3 ? cv.take<__bf16>(p.strm_pad * p.D) : nullptr;
   w.bias = cv.take<float>(p.strm_pad);
   w.part_m = cv.take<float>(int64_t(p.split) * p.stat_pad);
   w.part_l = cv.take<float>(int64_t(p.split) * p.stat_pad);
@@ -883,9 +887,9 @@ PassWs carve_pass(Carver& cv, const Plan& p) {
   return w;
 }
 
-size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim) {
+size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false) {
   Carver cv(nullptr, 0);
-  carve_pass(cv, make_plan(n_stat, n_strm, dim));
+  carve_pass(cv, make_plan(n_stat, n_strm, dim), x3);
   return cv.used();
 }
 
@@ -996,11 +1000,75 @@ int check_common(const float* q, int64_t ldq, int64_t n_rows, const float* c, in
 
 using namespace tt;
 
-extern "C" size_t tt_inbatch_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim) {
+namespace tt {
+namespace {
+size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3) {
   if (n_rows < 1 || n_cols < 1 || pick_dpad(dim) == 0) return 0;
-  const size_t a = pass_bytes(n_rows, n_cols, dim);
-  const size_t b = pass_bytes(n_cols, n_rows, dim);
+  const size_t a = pass_bytes(n_rows, n_cols, dim, x3);
+  const size_t b = pass_bytes(n_cols, n_rows, dim, x3);
   return a > b ? a : b;
+}
+
+// The rows / cols entries' bodies; x3: the bf16x3 form (residual planes of
+// both operands beside the bf16 images, inbatch_pass_kernel<D, MODE, true>).
+int xent_rows(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
+              int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset, float* lse, float* row_loss,
+              float* dq, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
+  if (rc) return rc;
+  TT_REQUIRE(lse && row_loss, "%s: NULL lse/row_loss", fn);
+  TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
+             "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
+  const Plan p = make_plan(n_rows, n_cols, dim);
+  Carver cv(workspace, workspace_bytes);
+  PassWs w = carve_pass(cv, p, x3);
+  if (!workspace || cv.used() > workspace_bytes)
+    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
+  hipStream_t st = to_stream(stream);
+  const PrepJob none{};
+  PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
+  jq.dst_lo = w.stat_lo;
+  jc.dst_lo = w.strm_lo;
+  if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
+  if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
+  PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, w.part_m, w.part_l, w.part_o,
+             w.stat_lo, w.strm_lo};
+  if ((rc = x3 ? launch_pass<0, true>(p, a, st) : launch_pass<0>(p, a, st))) return rc;
+  return combine_rows(p.D, st, w.part_m, w.part_l, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, logq, n_rows, dim,
+                      pos_offset, lse, row_loss, dq, nullptr);
+}
+
+int xent_cols(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+              const float* row_loss, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
+              int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
+  if (rc) return rc;
+  TT_REQUIRE(lse && dc, "%s: NULL lse/dc", fn);
+  TT_REQUIRE(pos_offset >= 0 && n_cols + pos_offset <= n_rows,
+             "%s: positives [pos_offset, pos_offset+n_cols) exceed n_rows", fn);
+  const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
+  Carver cv(workspace, workspace_bytes);
+  PassWs w = carve_pass(cv, p, x3);
+  if (!workspace || cv.used() > workspace_bytes)
+    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
+  hipStream_t st = to_stream(stream);
+  const PrepJob none{};
+  PrepJob jc = prep_job(c, ldc, n_cols, dim, w.stat), jq = prep_job(q, ldq, n_rows, dim, w.strm, lse, w.bias);
+  jc.dst_lo = w.stat_lo;
+  jq.dst_lo = w.strm_lo;
+  if ((rc = prep(p.D, jc, none, dim, p.stat_pad, st))) return rc;
+  if ((rc = prep(p.D, jq, none, dim, p.strm_pad, st))) return rc;
+  PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o,
+             w.stat_lo, w.strm_lo};
+  if ((rc = x3 ? launch_pass<1, true>(p, a, st) : launch_pass<1>(p, a, st))) return rc;
+  return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
+                      pos_offset, dc);
+}
+}  // namespace
+}  // namespace tt
+
+extern "C" size_t tt_inbatch_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim) {
+  return inbatch_ws_size(n_rows, n_cols, dim, false);
 }
 
 extern "C" int tt_inbatch_xent_rows(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
@@ -1008,24 +1076,8 @@ extern "C" int tt_inbatch_xent_rows(const float* q, int64_t ldq, int64_t n_rows,
                                     float* lse, float* row_loss, float* dq, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
-  if (rc) return rc;
-  TT_REQUIRE(lse && row_loss, "tt_inbatch_xent_rows: NULL lse/row_loss");
-  TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
-             "tt_inbatch_xent_rows: positives [pos_offset, pos_offset+n_rows) exceed n_cols");
-  const Plan p = make_plan(n_rows, n_cols, dim);
-  Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p);
-  if (!workspace || cv.used() > workspace_bytes)
-    return fail(TT_ERR_WORKSPACE, "tt_inbatch_xent_rows: workspace %zu < required %zu", workspace_bytes, cv.used());
-  hipStream_t st = to_stream(stream);
-  const PrepJob none{};
-  if ((rc = prep(p.D, prep_job(q, ldq, n_rows, dim, w.stat), none, dim, p.stat_pad, st))) return rc;
-  if ((rc = prep(p.D, prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias), none, dim, p.strm_pad, st))) return rc;
-  PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, w.part_m, w.part_l, w.part_o};
-  if ((rc = launch_pass<0>(p, a, st))) return rc;
-  return combine_rows(p.D, st, w.part_m, w.part_l, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, logq, n_rows, dim,
-                      pos_offset, lse, row_loss, dq, nullptr);
+  return xent_rows("tt_inbatch_xent_rows", false, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset, lse,
+                   row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1033,24 +1085,34 @@ extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows,
                                     const float* logq, int64_t pos_offset, float* dc, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
-  if (rc) return rc;
-  TT_REQUIRE(lse && dc, "tt_inbatch_xent_cols: NULL lse/dc");
-  TT_REQUIRE(pos_offset >= 0 && n_cols + pos_offset <= n_rows,
-             "tt_inbatch_xent_cols: positives [pos_offset, pos_offset+n_cols) exceed n_rows");
-  const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
-  Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p);
-  if (!workspace || cv.used() > workspace_bytes)
-    return fail(TT_ERR_WORKSPACE, "tt_inbatch_xent_cols: workspace %zu < required %zu", workspace_bytes, cv.used());
-  hipStream_t st = to_stream(stream);
-  const PrepJob none{};
-  if ((rc = prep(p.D, prep_job(c, ldc, n_cols, dim, w.stat), none, dim, p.stat_pad, st))) return rc;
-  if ((rc = prep(p.D, prep_job(q, ldq, n_rows, dim, w.strm, lse, w.bias), none, dim, p.strm_pad, st))) return rc;
-  PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o};
-  if ((rc = launch_pass<1>(p, a, st))) return rc;
-  return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
-                      pos_offset, dc);
+  return xent_cols("tt_inbatch_xent_cols", false, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
+                   pos_offset, dc, workspace, workspace_bytes, stream);
+}
+
+// The same two entries with fp32-faithful products (X3, as
+// tt_inbatch_softmax_xent_x3 below): what every rank of the global-negatives
+// step runs under TT_INBATCH_X3=1.  Rectangular launches of the X3 pass:
+// stationary rows padded to 128, streamed rows to 64, any pos_offset.
+extern "C" size_t tt_inbatch_x3_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim) {
+  return inbatch_ws_size(n_rows, n_cols, dim, true);
+}
+
+extern "C" int tt_inbatch_xent_rows_x3(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
+                                       int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset,
+                                       float* lse, float* row_loss, float* dq, void* workspace,
+                                       size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  return xent_rows("tt_inbatch_xent_rows_x3", true, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset, lse,
+                   row_loss, dq, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tt_inbatch_xent_cols_x3(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+                                       const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
+                                       int32_t dim, const float* logq, int64_t pos_offset, float* dc,
+                                       void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  return xent_cols("tt_inbatch_xent_cols_x3", true, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
+                   pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------

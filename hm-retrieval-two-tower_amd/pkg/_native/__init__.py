@@ -280,6 +280,17 @@ _PROTOS = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_float, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "tt_inbatch_x3_workspace_size": (c_size_t, [c_int64, c_int64, c_int32]),
+    "tt_inbatch_xent_rows_x3": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_xent_cols_x3": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "tt_bruteforce_index_bytes": (c_size_t, [c_int64, c_int32]),
     "tt_bruteforce_build": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "tt_bruteforce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),

@@ -794,8 +794,9 @@ def _opt_ptr(t: Optional[torch.Tensor], name: str, n: int) -> Optional[int]:
 
 
 def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], pos_offset: int = 0,
-                 want_dq: bool = True):
-    """Row pass: (lse [R], row_loss [R], dq [R,E] or None)."""
+                 want_dq: bool = True, x3: bool = False):
+    """Row pass: (lse [R], row_loss [R], dq [R,E] or None).  x3: fp32-faithful
+    products (tt_inbatch_xent_rows_x3, as inbatch_fused(x3=True))."""
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
     ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
@@ -804,32 +805,39 @@ def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
     if c.shape[1] != E:
         raise ValueError("q and c must share the embedding size")
     L = lib()
-    ws = Workspace.get(L.tt_inbatch_workspace_size(R, C, E), q.device, "inbatch")
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3)
     lse = torch.empty(R, dtype=torch.float32, device=q.device)
     row_loss = torch.empty(R, dtype=torch.float32, device=q.device)
     dq = torch.empty(R, E, dtype=torch.float32, device=q.device) if want_dq else None
-    check(L.tt_inbatch_xent_rows(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
-                                 pos_offset, lse.data_ptr(), row_loss.data_ptr(),
-                                 dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(), _stream()))
+    fn = L.tt_inbatch_xent_rows_x3 if x3 else L.tt_inbatch_xent_rows
+    check(fn(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C), pos_offset, lse.data_ptr(),
+             row_loss.data_ptr(), dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(), _stream()))
     return lse, row_loss, dq
 
 
+def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool) -> torch.Tensor:
+    """The rows / cols entries' workspace (x3: the larger one of its own)."""
+    if x3:
+        return Workspace.get(L.tt_inbatch_x3_workspace_size(R, C, E), device, "inbatch_x3")
+    return Workspace.get(L.tt_inbatch_workspace_size(R, C, E), device, "inbatch")
+
+
 def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
-                 pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None, x3: bool = False) -> torch.Tensor:
     """Column pass: dc [C,E] from every row's q [R,E], lse [R] and (optional,
-    for the exact 1 - P_pos of confident rows) row_loss [R]."""
+    for the exact 1 - P_pos of confident rows) row_loss [R].  x3: fp32-faithful
+    products (tt_inbatch_xent_cols_x3)."""
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
     ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
     R, E = q.shape
     C = c.shape[0]
     L = lib()
-    ws = Workspace.get(L.tt_inbatch_workspace_size(R, C, E), q.device, "inbatch")
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3)
     dc = torch.empty(C, E, dtype=torch.float32, device=q.device)
-    check(L.tt_inbatch_xent_cols(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R),
-                                 c.data_ptr(), ldc, C, E,
-                                 _opt_ptr(logq, "logq", C), pos_offset, dc.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _stream()))
+    fn = L.tt_inbatch_xent_cols_x3 if x3 else L.tt_inbatch_xent_cols
+    check(fn(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
+             _opt_ptr(logq, "logq", C), pos_offset, dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return dc
 
 

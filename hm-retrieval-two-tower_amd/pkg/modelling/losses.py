@@ -11,6 +11,7 @@ gradient.  The [B, B] score matrix never exists.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 from typing import Optional
@@ -24,12 +25,18 @@ __all__ = ["InBatchSoftmaxCrossEntropy", "inbatch_softmax_xent", "towers_inbatch
 
 
 def x3_scores() -> bool:
-    """TT_INBATCH_X3=1 (read at each call): the single-device in-batch loss
-    with fp32-faithful products (hip_ops.inbatch_fused(x3=True): S and P.V
-    as bf16x3 products) — the reference's fp32 logits and gradients to
-    ~2^-16, dQ / dC within 1e-3 of fp64 at trained score magnitudes; ~3x the
-    passes' time.  The
-    default is the bf16-operand contract (include/tt.h K5-K7)."""
+    """TT_INBATCH_X3=1 (read at each call): the in-batch loss with
+    fp32-faithful products (S and P.V as bf16x3 products) on every path: the
+    single-device step (hip_ops.inbatch_fused(x3=True)), the global-negatives
+    data-parallel step (global_inbatch_grads: the fused entry at one rank,
+    hip_ops.inbatch_rows / inbatch_cols(x3=True) on every rank otherwise) and
+    the no-grad evaluation loss (inbatch_softmax_xent).  Accuracy at trained
+    score magnitudes (|S| ~ 100), where the default bf16 operands drift to
+    ~8e-3: asserted 1e-3 in dQ/dC and 1e-4 in loss against fp64, measured
+    <= 8.5e-6.  2.0-2.4x the default loss's time.  A captured
+    step keeps the mode it was captured with: the flag is read when the step
+    runs eagerly, not when its graph replays.  The default is the
+    bf16-operand contract (include/tt.h K5-K7)."""
     return os.environ.get("TT_INBATCH_X3", "0") == "1"
 
 
@@ -164,7 +171,9 @@ class _TowersInBatchXent(torch.autograd.Function):
         side = _tower_stream(qi.device) if TOWER_STREAMS else main
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
-        ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if SPLIT_PREP else None
+        # (not under x3_scores(): that entry prepares its operands itself)
+        split_prep = SPLIT_PREP and not x3_scores()
+        ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
         with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
             ca = stack_c.forward_acts(ci, flat_c)
@@ -224,7 +233,7 @@ class _TowersInBatchXent(torch.autograd.Function):
 
 
 def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], comm,
-                         rows=None, cols=None):
+                         rows=None, cols=None, x3: Optional[bool] = None):
     """This rank's share of the in-batch loss over the GLOBAL batch
     (two_tower_model.py:113-122 with the batch split over the ranks: row i's
     negatives are every candidate of every rank).  q, c: this rank's [b, E]
@@ -234,14 +243,18 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     / d c of its candidates.  The rows pass scores the local queries against
     all candidates; the cols pass scores all queries (with their lse) against
     the local candidates, so every gradient is summed inside one kernel in a
-    fixed order (no cross-rank reduction of partial sums)."""
+    fixed order (no cross-rank reduction of partial sums).  x3: fp32-faithful
+    products in the library's entries (None: x3_scores(), the flag read at
+    this call); injected rows / cols are called as they are."""
+    if x3 is None:
+        x3 = x3_scores()
     if WORLD1_FUSED and comm.world == 1 and rows is None and cols is None and not getattr(comm, "always", False):
         # one rank: its rows are every row and its columns every column — the
         # single-device entry (one shared preparation of q and c for both passes)
-        _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq)
+        _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3)
         return row_loss, dq, dc
-    rows = rows or hip_ops.inbatch_rows
-    cols = cols or hip_ops.inbatch_cols
+    rows = rows or (functools.partial(hip_ops.inbatch_rows, x3=True) if x3 else hip_ops.inbatch_rows)
+    cols = cols or (functools.partial(hip_ops.inbatch_cols, x3=True) if x3 else hip_ops.inbatch_cols)
     b = q.shape[0]
     off = comm.rank * b
     C = comm.all_gather(c)                                     # [G b, E]
@@ -326,7 +339,8 @@ def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / q.shape[0]
     if not q.requires_grad and not c.requires_grad:
-        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False)
+        # the scores the training loss is computed from, in either mode
+        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores())
         return hip_ops.loss_sum(row_loss, scale)
     return _InBatchXent.apply(q, c, logq, scale)
 
