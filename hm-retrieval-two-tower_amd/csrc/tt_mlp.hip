@@ -1,5 +1,6 @@
 // K4 (tower MLP), row-streaming form: C = epi(maskA(A) . B) for a tall fp32
-// activation A [M, K] and a small weight operand B [K, N] (K, N <= 288),
+// activation A [M, K] and a small weight operand B [K, N] (N <= 4096; K any,
+// M * lda < 2^30 for the 32-bit buffer offsets),
 // the shape of every Dense-layer GEMM of the towers except the weight
 // gradients (/root/reference/pkg/modelling/models/tower.py:41-49):
 //   forward   h = relu(x W + b)                       B = W,   epi bias + relu
@@ -25,6 +26,28 @@
 // column blocks per wave row), so the compiler's vmcnt waits are exact.
 // 4 waves; wave w computes rows 0..63 x the 32-column blocks w, w+4, w+8
 // (each B fragment is loaded by exactly one wave of the workgroup).
+//
+// N > 384 (a workgroup keeps at most 3 blocks per wave = 384 columns in
+// accumulators and a 97 KiB output tile): the launch covers (row blocks) x
+// (column groups).  The image is padded to whole 128-column units (4 blocks,
+// one per wave); G = ceil(units / 3) groups take base = units / G units each,
+// the first units % G one more, and a workgroup runs the NCB = 1, 2 or 3
+// instantiation of the same block code for ITS group's unit count, chosen at
+// run time (a workgroup-uniform branch, as mlp_rows_pair_kernel chooses
+// between its two problems).  Chosen over a uniform NCB with guarded blocks
+// because a group then only ever addresses whole units below NBp: no image
+// block past the padding can be loaded, the main loop stays branch-free, no
+// MFMAs are spent on blocks that do not exist (772 columns = 7 units run as
+// 3 + 2 + 2, not 3 x 3), and the even deal keeps N <= 512 at two 2-unit groups
+// whose 66.5 KiB tile lets two workgroups share a CU.  A group offsets only
+// the image block, the bias / cmask / C / parts column and the store width;
+// the A stages, the k-steps, their order and the three MFMAs per step are the
+// narrow kernel's, so an output element does not depend on the grouping (the
+// result on a 128-aligned window equals the narrow kernel on that slice of
+// B, bit for bit).  The groups of a row block re-read its A rows: while the
+// image is smaller than an XCD's L2, block ids are laid out so they run back
+// to back on one XCD; a larger image runs group by group (rows_order).
+// N <= 384 launches exactly the ungrouped kernels.
 #include <type_traits>
 
 #include <cstdlib>
@@ -44,7 +67,8 @@ constexpr int kMlpBM = TT_MLP_BM;  // rows per workgroup (32 or 64)
 constexpr int kMlpRB = kMlpBM / 32;  // 32-row MFMA blocks per wave
 constexpr int kMlpUQ = kMlpBM / 16;  // A rows per thread per stage
 constexpr int kMlpBK = 64;       // depth per A stage (4 MFMA k-steps)
-constexpr int kMlpMaxCB = 3;     // 32-column blocks per wave (N <= 384)
+constexpr int kMlpMaxCB = 3;     // 32-column blocks per wave: 384 columns per workgroup
+constexpr int kMlpMaxN = 4096;   // widest B (tt_mlp_wgrad's bound); over 384 in column groups
 
 
 struct MlpArgs {
@@ -62,7 +86,9 @@ struct MlpArgs {
   int64_t ldcm;
   float* C;
   int64_t ldc;
-  float* parts;        // optional [gridDim.x][N]: per-workgroup column sums of C
+  float* parts;        // optional [row blocks][N]: per-workgroup column sums of C
+  int G;               // column groups (1: N <= 384, the whole width in one workgroup)
+  int order;           // grouped launches: block id -> (row block, group), see mlp_rows_grouped
 };
 
 // Raw buffer resource over `bytes` bytes: loads past the end return 0.
@@ -105,9 +131,14 @@ struct MlpSmem {
 };
 
 // One workgroup's rows [bid * kMlpBM, +kMlpBM) of one problem; smem_raw holds
-// MlpSmem<NCB>::BYTES.
-template <int NCB, bool HAS_MASK>
-__device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t bid, char* smem_raw) {
+// MlpSmem<NCB>::BYTES.  GROUPED: the workgroup owns the 4 NCB image blocks
+// from cb0 (a multiple of 4, cb0 + 4 NCB <= NBp), i.e. columns [32 cb0,
+// min(N, 32 cb0 + 128 NCB)) of B, bias, cmask, C and parts; everything else
+// (the A stages, the k-steps and their order, the three MFMAs per step) is the
+// ungrouped code, so an output element does not depend on the grouping.
+template <int NCB, bool HAS_MASK, bool GROUPED = false>
+__device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t bid, char* smem_raw,
+                                               const int cb0 = 0) {
   constexpr int OUT_LD = MlpSmem<NCB>::OUT_LD;
   char (*smem)[2 * kMlpBM * 128] = reinterpret_cast<char (*)[2 * kMlpBM * 128]>(smem_raw);
   const int tid = threadIdx.x;
@@ -155,7 +186,7 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   };
 
   // ---- B fragments: k-step ks, block i (column block wave + 4 i), plane p ----
-  const bf16x8* img = reinterpret_cast<const bf16x8*>(a.img) + lane;
+  const bf16x8* img = reinterpret_cast<const bf16x8*>(a.img) + lane + (GROUPED ? cb0 * 2 * 64 : 0);
   const int64_t kstride = static_cast<int64_t>(a.NBp) * 2 * 64;  // bf16x8 per k-step
   bf16x8 bq[4][NCB][2];  // k-step ks in slot ks % 4 (static under the 2-stage unroll)
   auto load_b = [&](int ks, auto slot_c) {
@@ -231,10 +262,11 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   // stores of C with the epilogue mask read the same way (coalesced).
   __syncthreads();  // every wave is done reading the A stages
   float* tile = reinterpret_cast<float*>(smem_raw);
+  const int c0 = GROUPED ? cb0 * 32 : 0;  // first column of the group: tile column c is column c0 + c
 #pragma unroll
   for (int i = 0; i < NCB; ++i) {
     const int col = (wave + 4 * i) * 32 + l32;
-    const float b = (a.bias && col < a.N) ? a.bias[col] : 0.0f;
+    const float b = (a.bias && c0 + col < a.N) ? a.bias[c0 + col] : 0.0f;
 #pragma unroll
     for (int rb = 0; rb < kMlpRB; ++rb)
 #pragma unroll
@@ -246,13 +278,16 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   }
   __syncthreads();
   const int64_t rows = a.M - m0 < kMlpBM ? a.M - m0 : kMlpBM;
-  float* C = a.C + m0 * a.ldc;
-  const float* cm = a.cmask ? a.cmask + m0 * a.ldcm : nullptr;
+  float* C = a.C + m0 * a.ldc + c0;
+  const float* cm = a.cmask ? a.cmask + m0 * a.ldcm + c0 : nullptr;
+  // this workgroup's columns: all N, or the group's (c0 is a multiple of 128,
+  // so the group's rows are 16-B aligned exactly when the problem's are)
+  const int N = GROUPED ? (a.N - c0 < NCB * 128 ? a.N - c0 : NCB * 128) : a.N;
   // 16-B stores of whole rows; a ragged N writes its row's padding columns
   // (zeros: the image is zero there) when the row pitch has room for them
-  const int n4 = (a.N + 3) / 4 * 4;
-  const bool v4 = (a.ldc % 4 == 0) && (a.ldc >= n4) && (reinterpret_cast<uintptr_t>(a.C) % 16 == 0) &&
-                  (!cm || ((a.N % 4 == 0) && (a.ldcm % 4 == 0) && (reinterpret_cast<uintptr_t>(a.cmask) % 16 == 0)));
+  const int n4 = (N + 3) / 4 * 4;
+  const bool v4 = (a.ldc % 4 == 0) && (a.ldc >= c0 + n4) && (reinterpret_cast<uintptr_t>(a.C) % 16 == 0) &&
+                  (!cm || ((N % 4 == 0) && (a.ldcm % 4 == 0) && (reinterpret_cast<uintptr_t>(a.cmask) % 16 == 0)));
   if (v4) {
     const int per_row = n4 / 4;
     for (int idx = tid; idx < rows * per_row; idx += kMlpThreads) {
@@ -267,8 +302,8 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
       *reinterpret_cast<f32x4*>(C + row * a.ldc + c4) = v;
     }
   } else {
-    for (int idx = tid; idx < rows * a.N; idx += kMlpThreads) {
-      const int row = idx / a.N, c = idx - row * a.N;
+    for (int idx = tid; idx < rows * N; idx += kMlpThreads) {
+      const int row = idx / N, c = idx - row * N;
       float v = tile[row * OUT_LD + c];
       if (cm && !(cm[row * a.ldcm + c] > 0.0f)) v = 0.0f;
       if (cm && a.parts) tile[row * OUT_LD + c] = v;
@@ -280,17 +315,76 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   // output gradient): this workgroup's rows in order; mlp_colsum_kernel then
   // adds the workgroups' partials in workgroup order (deterministic).
   __syncthreads();
-  for (int c = tid; c < a.N; c += kMlpThreads) {
+  for (int c = tid; c < N; c += kMlpThreads) {
     float sum = 0.0f;
     for (int row = 0; row < rows; ++row) sum += tile[row * OUT_LD + c];  // already masked
-    a.parts[bid * a.N + c] = sum;
+    a.parts[bid * a.N + c0 + c] = sum;
   }
+}
+
+// N > 384: workgroup `id` of a problem's nrb * G, one (row block, column group)
+// each.  The NBp / 4 128-column units are dealt evenly, G = ceil(units / 3)
+// groups of base or base + 1 units (the first `units % G` groups get the extra
+// one), and each group runs the instantiation for its own unit count, picked
+// at run time (workgroup-uniform) like the pair kernel's two problems: every
+// group touches only whole units below NBp, so no image block past the
+// padding is loaded and no guard sits in the main loop.  XMAX (2 or 3) is the
+// largest group of the launch, which sizes the LDS: N <= 512 is two 2-unit
+// groups with a 66.5 KiB tile, two workgroups per CU.
+// a.order (chosen by rows_order on the host):
+// 0: row-major over the XCDs.  Block ids are dealt round-robin to the 8 XCDs;
+// XCD x takes a contiguous chunk of the (row block, group) list in its
+// dispatch order (chunks differ by at most one when 8 does not divide the
+// count), so the G groups of a row block run back to back on one XCD and the
+// later ones read the block's A rows from that XCD's L2.
+// 1: group-major, id = g * nrb + rb.
+__device__ __forceinline__ int mlp_xcd_chunk(int id, int n) {
+  const int q = n >> 3, r = n & 7, x = id & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
+}
+
+template <int XMAX, bool HAS_MASK>
+__device__ __forceinline__ void mlp_rows_grouped(const MlpArgs& a, const int id, char* smem_raw) {
+  const int nrb = static_cast<int>((a.M + kMlpBM - 1) / kMlpBM);
+  int rb, g;
+  if (a.order == 0) {
+    const int t = mlp_xcd_chunk(id, nrb * a.G);
+    rb = t / a.G;
+    g = t - rb * a.G;
+  } else {
+    g = id / nrb;
+    rb = id - g * nrb;
+  }
+  const int units = a.NBp >> 2, base = units / a.G, extra = units - base * a.G;
+  const int ncb = base + (g < extra ? 1 : 0);
+  const int cb0 = 4 * (g * base + (g < extra ? g : extra));
+  if (ncb == 1) mlp_rows_block<1, HAS_MASK, true>(a, rb, smem_raw, cb0);
+  else if (XMAX == 2 || ncb == 2) mlp_rows_block<2, HAS_MASK, true>(a, rb, smem_raw, cb0);
+  else mlp_rows_block<3, HAS_MASK, true>(a, rb, smem_raw, cb0);
 }
 
 template <int NCB, bool HAS_MASK>
 __global__ void __launch_bounds__(kMlpThreads) mlp_rows_kernel(const MlpArgs a) {
   __shared__ __attribute__((aligned(16))) char smem_raw[MlpSmem<NCB>::BYTES];
   mlp_rows_block<NCB, HAS_MASK>(a, blockIdx.x, smem_raw);
+}
+
+template <int XMAX, bool HAS_MASK>
+__global__ void __launch_bounds__(kMlpThreads) mlp_rows_grouped_kernel(const MlpArgs a) {
+  __shared__ __attribute__((aligned(16))) char smem_raw[MlpSmem<XMAX>::BYTES];
+  mlp_rows_grouped<XMAX, HAS_MASK>(a, blockIdx.x, smem_raw);
+}
+
+// Two problems in one launch when at least one is wider than 384: blocks
+// [0, split) are a0's nrb0 * G0 (row block, group) pairs, the rest a1's (a
+// narrow problem is one group of NBp / 4 units).
+template <int XMAX, bool HAS_MASK>
+__global__ void __launch_bounds__(kMlpThreads) mlp_rows_grouped_pair_kernel(const MlpArgs a0, const MlpArgs a1,
+                                                                            const int split) {
+  __shared__ __attribute__((aligned(16))) char smem_raw[MlpSmem<XMAX>::BYTES];
+  const int b = blockIdx.x;
+  if (b < split) mlp_rows_grouped<XMAX, HAS_MASK>(a0, b, smem_raw);
+  else mlp_rows_grouped<XMAX, HAS_MASK>(a1, b - split, smem_raw);
 }
 
 // Two independent problems in one launch (the two towers' layers): blocks
@@ -946,8 +1040,24 @@ extern "C" size_t tt_mlp_rows_workspace_size(int64_t M, int32_t N) {
   return static_cast<size_t>(ceil_div(M, kMlpBM)) * N * sizeof(float);
 }
 
+// The block order of a grouped launch (mlp_rows_grouped).  Concurrent
+// workgroups of order 0 cover every group, so each XCD's L2 streams the whole
+// B image; those of order 1 share one group's <= 384 columns of it but
+// re-read A from further away.  Measured: order 0 wins
+// while the image is smaller than an XCD's 4 MiB L2 (0.5-2.4 us per launch at
+// M = 16384), order 1 from there on (5 % at 4 MiB, 9-10 % at 8 and 32 MiB).
+// TT_MLP_ROWS_ORDER = "xcd" / "group" forces order 0 / 1 (read at every
+// call, so one process can time both); -1: set to anything else.
+static int rows_order(size_t image_bytes) {
+  const char* e = std::getenv("TT_MLP_ROWS_ORDER");
+  if (!e || !*e) return image_bytes < (size_t(4) << 20) ? 0 : 1;
+  if (!std::strcmp(e, "xcd")) return 0;
+  return std::strcmp(e, "group") ? -1 : 1;
+}
+
 // Validates one tt_mlp_rows problem (no colsum) into its kernel arguments;
-// *ncb = column blocks per wave.  TT_OK or the error code (message set).
+// ncb = column blocks per wave of its widest column group (a.G groups: one
+// for N <= 384).  TT_OK or the error code (message set).
 static int rows_setup(const char* fn, const float* A, int64_t lda, const float* amask, int64_t ldam,
                       const float* scale, int64_t M, int32_t K, const void* img, int32_t N, const float* bias,
                       int32_t relu, const float* cmask, int64_t ldcm, float* C, int64_t ldc, MlpArgs& a, int& ncb) {
@@ -955,7 +1065,7 @@ static int rows_setup(const char* fn, const float* A, int64_t lda, const float* 
   TT_REQUIRE(img && (M == 0 || (A && C)), "%s: NULL A/img/C", fn);
   TT_REQUIRE(M >= 0 && K >= 1 && N >= 1, "%s: bad M/K/N", fn);
   const int NB = mlp_nb(N);
-  TT_REQUIRE(NB <= 4 * kMlpMaxCB, "%s: N=%d > %d unsupported", fn, N, 32 * 4 * kMlpMaxCB);
+  if (N > kMlpMaxN) return fail(TT_ERR_UNSUPPORTED, "%s: N=%d > %d unsupported", fn, N, kMlpMaxN);
   TT_REQUIRE(M * lda < (int64_t(1) << 30) && (!amask || M * ldam < (int64_t(1) << 30)),
              "%s: operand too large for 32-bit buffer offsets", fn);
   TT_REQUIRE(lda >= K && ldc >= N && (!amask || ldam >= K) && (!cmask || ldcm >= N),
@@ -981,13 +1091,23 @@ static int rows_setup(const char* fn, const float* A, int64_t lda, const float* 
   a.ldcm = ldcm;
   a.C = C;
   a.ldc = ldc;
-  ncb = NB / 4;
+  a.G = static_cast<int>(ceil_div(NB / 4, kMlpMaxCB));
+  ncb = static_cast<int>(ceil_div(NB / 4, a.G));
+  if (a.G > 1) {
+    a.order = rows_order(tt_mlp_pack_bytes(K, N));
+    TT_REQUIRE(a.order >= 0, "%s: TT_MLP_ROWS_ORDER must be xcd or group", fn);
+  }
   return TT_OK;
 }
 
 template <bool HM>
 static void launch_rows(const MlpArgs& a, int ncb, hipStream_t st) {
-  const dim3 grid(static_cast<unsigned>(ceil_div(a.M, kMlpBM)));
+  const dim3 grid(static_cast<unsigned>(ceil_div(a.M, kMlpBM) * a.G));
+  if (a.G > 1) {  // N > 384: (row blocks) x (column groups), ncb is 2 or 3
+    if (ncb == 2) hipLaunchKernelGGL((mlp_rows_grouped_kernel<2, HM>), grid, dim3(kMlpThreads), 0, st, a);
+    else hipLaunchKernelGGL((mlp_rows_grouped_kernel<3, HM>), grid, dim3(kMlpThreads), 0, st, a);
+    return;
+  }
   if (ncb == 1) hipLaunchKernelGGL((mlp_rows_kernel<1, HM>), grid, dim3(kMlpThreads), 0, st, a);
   else if (ncb == 2) hipLaunchKernelGGL((mlp_rows_kernel<2, HM>), grid, dim3(kMlpThreads), 0, st, a);
   else hipLaunchKernelGGL((mlp_rows_kernel<3, HM>), grid, dim3(kMlpThreads), 0, st, a);
@@ -1003,8 +1123,14 @@ static void launch_rows_pair1(const MlpArgs& a0, const MlpArgs& a1, int ncb1, in
 
 template <bool HM>
 static void launch_rows_pair(const MlpArgs& a0, int ncb0, const MlpArgs& a1, int ncb1, hipStream_t st) {
-  const int split = static_cast<int>(ceil_div(a0.M, kMlpBM));
-  const dim3 grid(static_cast<unsigned>(split + ceil_div(a1.M, kMlpBM)));
+  const int split = static_cast<int>(ceil_div(a0.M, kMlpBM) * a0.G);
+  const dim3 grid(static_cast<unsigned>(split + ceil_div(a1.M, kMlpBM) * a1.G));
+  if (a0.G > 1 || a1.G > 1) {  // a wide problem: the grouped blocks of both (a wide one's ncb is 2 or 3)
+    if (ncb0 < 3 && ncb1 < 3)
+      hipLaunchKernelGGL((mlp_rows_grouped_pair_kernel<2, HM>), grid, dim3(kMlpThreads), 0, st, a0, a1, split);
+    else hipLaunchKernelGGL((mlp_rows_grouped_pair_kernel<3, HM>), grid, dim3(kMlpThreads), 0, st, a0, a1, split);
+    return;
+  }
   if (ncb0 == 1) launch_rows_pair1<1, HM>(a0, a1, ncb1, split, grid, st);
   else if (ncb0 == 2) launch_rows_pair1<2, HM>(a0, a1, ncb1, split, grid, st);
   else launch_rows_pair1<3, HM>(a0, a1, ncb1, split, grid, st);
@@ -1049,6 +1175,7 @@ extern "C" int tt_mlp_rows_pair(const tt_mlp_rows_problem* p, tt_stream_t stream
                               q.bias, q.relu, q.cmask, q.ldcm, q.C, q.ldc, a[i], ncb[i]);
     if (rc != TT_OK) return rc;
   }
+  if (a[0].M == 0 && a[1].M == 0) return TT_OK;  // nothing to launch (as tt_mlp_rows)
   hipStream_t st = to_stream(stream);
   const bool hm0 = a[0].amask != nullptr, hm1 = a[1].amask != nullptr;
   if (a[0].M == 0 || a[1].M == 0 || hm0 != hm1) {  // one problem, or masks differ: one launch each

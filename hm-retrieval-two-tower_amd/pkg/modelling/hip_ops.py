@@ -1181,7 +1181,8 @@ def mlp_rows(a: torch.Tensor, img: torch.Tensor, k: int, n: int, out: torch.Tens
              bias: Optional[torch.Tensor] = None, relu: bool = False,
              cmask: Optional[torch.Tensor] = None, colsum: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M, n] = epi(maskA(a[:, :k]) . B) with B packed by mlp_pack (tt_mlp_rows);
-    colsum (a contiguous [n] tensor): also the column sums of out."""
+    colsum (a contiguous [n] tensor): also the column sums of out.  n <= 4096
+    (over 384 the one launch covers column groups, same arithmetic)."""
     M = _check_rows(a, k, n, out, amask, cmask, bias)
     ws = None
     if colsum is not None:

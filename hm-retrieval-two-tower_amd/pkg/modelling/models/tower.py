@@ -83,17 +83,31 @@ class _DenseStackFn(torch.autograd.Function):
 
 
 class DenseStack:
-    """relu(x W_l + b_l) for each layer; parameters are views of `flat`."""
+    """relu(x W_l + b_l) for each layer; parameters are views of `flat`.
 
-    def __init__(self, in_dim: int, units: List[int], device: torch.device, generator: torch.Generator):
+    max_width bounds every layer's fan-in and units.  Two values are in use:
+    the bare constructor keeps 384, the widest layer that tt_mlp_rows runs as
+    one workgroup per 64 rows (the whole output width in one workgroup's
+    accumulators — the shapes the step was tuned and measured at), so a
+    caller that builds a stack directly opts in to wider layers knowingly;
+    Tower passes MAX_WIDTH = 4096, the kernels' own bound (tt_mlp_rows in
+    column groups of <= 384, tt_mlp_wgrad's Ka, N <= 4096), so the public
+    API takes any width up to it.  There is no fallback GEMM above either."""
+
+    MAX_WIDTH = 4096  # tt_mlp_rows / tt_mlp_wgrad: N, Ka <= 4096
+
+    def __init__(self, in_dim: int, units: List[int], device: torch.device, generator: torch.Generator, *,
+                 max_width: int = 384):
+        if not 1 <= max_width <= self.MAX_WIDTH:
+            raise ValueError(f"max_width={max_width} must be in 1..{self.MAX_WIDTH} (tt_mlp_rows, tt_mlp_wgrad)")
         self.layout: List[Tuple[int, int, int, int]] = []  # (w_off, fan_in, fan_out, b_off)
         off = 0
         fan_in = in_dim
         for u in units:
-            if not 1 <= u <= 384 or fan_in > 384:
-                # tt_mlp_rows' output width (the forward's units, the input
-                # gradient's fan-in) is at most 384: no fallback GEMM
-                raise ValueError(f"Dense layer {fan_in} -> {u}: widths must be in 1..384 (tt_mlp_rows)")
+            if not 1 <= u <= max_width or fan_in > max_width:
+                # tt_mlp_rows' output width is the forward's units and the
+                # input gradient's fan-in: no fallback GEMM
+                raise ValueError(f"Dense layer {fan_in} -> {u}: widths must be in 1..{max_width} (tt_mlp_rows)")
             self.layout.append((off, fan_in, u, off + fan_in * u))
             off += fan_in * u + u
             fan_in = u
@@ -176,7 +190,9 @@ class DenseStack:
     def _wgrad_fits(self, li: int, g: torch.Tensor, acts: List[torch.Tensor]) -> bool:
         """tt_mlp_wgrad's alignment contract for layer li: N % 4 == 0 and
         16-B aligned rows of its activations, gradient and mask operands
-        (widths over 384 are refused when the stack is built)."""
+        (widths over max_width <= 4096, the kernel's own Ka / N bound, are
+        refused when the stack is built, so the width checks below never
+        fail for a built stack)."""
         _, fi, fo, _ = self.layout[li]
         for t in (g, acts[li], acts[-1]):
             if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
@@ -397,6 +413,10 @@ class Tower(AbstractKerasModel):
         Size used for taking the dot product with the other tower.
     hidden_units: Optional[List[int]]
         Optional hidden units.
+
+    The input width (the features' concatenated embeddings and numerics) and
+    every layer's units may be up to 4096 (DenseStack.MAX_WIDTH); a wider
+    layer raises ValueError.
     """
 
     def __init__(self, features: List[Feature], joint_embedding_size: int,
@@ -413,7 +433,10 @@ class Tower(AbstractKerasModel):
     def _init_layers(self) -> None:
         self.input_layer = InputLayer(self.features, self.device, self._generator)
         units = list(self.hidden_units or []) + [self.joint_embedding_size]
-        self.dense = DenseStack(self.input_layer.output_dim, units, self.device, self._generator)
+        # the public API takes every width the kernels do (DenseStack: why the
+        # bare constructor's default is lower)
+        self.dense = DenseStack(self.input_layer.output_dim, units, self.device, self._generator,
+                                max_width=DenseStack.MAX_WIDTH)
         self.model_layers = [self.input_layer, self.dense]
 
     def call(self, x: Dict[str, torch.Tensor], training: bool = True) -> torch.Tensor:

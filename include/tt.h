@@ -601,8 +601,15 @@ int tt_batch_take(const void* src, int64_t src_ld, int32_t ncols, const int64_t*
 /* ------------------------------------------------------------------------ *
  * K4  Tower MLP, row-streaming GEMM (Dense layers, pkg/modelling/models/
  * tower.py:41-49): C[M, N] = epi(maskA(A) . B) for a tall fp32 activation
- * A [M, K] and a small weight operand B [K, N] (N <= 384), on bf16x3 MFMA
+ * A [M, K] and a small weight operand B [K, N], on bf16x3 MFMA
  * (fp32-faithful: a_lo b_hi + a_hi b_lo + a_hi b_hi, fp32 accumulation).
+ * Bounds: N <= 4096 (tt_mlp_wgrad's; above it TT_ERR_UNSUPPORTED) and
+ * M * lda < 2^30, M * ldam < 2^30 (32-bit buffer offsets); K is bounded only
+ * by lda.  A workgroup holds 64 rows x at most 384 columns: N <= 384 is one
+ * workgroup per 64 rows, a wider N runs (row blocks) x ceil(N / 384) column
+ * groups in the same launch, each output element with the arithmetic of the
+ * narrow kernel (the result over any 128-aligned column window equals a call
+ * on that window's slice of B bit for bit).
  *   maskA (amask != NULL):  A := (amask > 0) ? A * (*scale) : 0   (ReluGrad)
  *   epilogue:  + bias[n] (bias != NULL), relu (relu != 0), then
  *              C := (cmask > 0) ? C : 0 (cmask != NULL)
@@ -660,8 +667,9 @@ int tt_mlp_wgrad_adagrad(const float* A, int64_t lda, const float* G, int64_t ld
  * tower are independent chains of the same shape of work: one stream, no
  * fork/join).  p points at 2 problems with tt_mlp_rows' / tt_mlp_wgrad's
  * arguments and contracts (rows: no colsum); the results equal two single
- * calls bit for bit.  Replaces the two towers' Dense layers of
- * two_tower_model.py:90-91 (query_tower(x), candidate_tower(x)). */
+ * calls bit for bit.  The two rows problems may differ in width and in their
+ * number of column groups (N <= 4096 each).  Replaces the two towers' Dense
+ * layers of two_tower_model.py:90-91 (query_tower(x), candidate_tower(x)). */
 typedef struct {
   const float* A;
   int64_t lda;
