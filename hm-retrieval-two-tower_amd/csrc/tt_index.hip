@@ -97,6 +97,9 @@ constexpr float kTiny = 1e-30f;
 #define TT_LIST_BUDGET (size_t(2) << 30)
 #endif
 constexpr size_t kListBudget = TT_LIST_BUDGET;   // bytes of screened lists per chunk
+#ifndef TT_SCAN_PROBE
+#define TT_SCAN_PROBE 0  // 1, 2: scan_kernel timing probes without the filter (tools/build_variant.sh builds them)
+#endif
 
 enum : int { kQZero = 1, kQRel = 2 };
 
@@ -390,11 +393,11 @@ __device__ float bins_select(const float (&ba)[16], const float (&bb)[16], int j
   return (t > -INFINITY) ? t : -INFINITY;  // NaN (no prefix found) -> keep everything
 }
 
-// The estimate pass (phase 1) over the split's spread sample tiles: writes
-// tau[q][split].  (scan_kernel below is phase 2.)
+// The estimate pass (phase 1 of the screen) over the split's spread sample
+// tiles: keeps the bins and writes them (pooled estimate) or tau[q][split].
+// (scan_kernel below is phase 2.)
 template <int D>
 __global__ void __launch_bounds__(kSThreads) sample_kernel(const ScreenArgs a) {
-  constexpr bool SAMPLE = true;
   constexpr int KS = D / 16, RB = D * 2;
   constexpr int TILE_BYTES = kCTile * RB;                 // 16 KiB at D = 128
   constexpr int PIECES = TILE_BYTES / 1024;               // 1 KiB LDS-DMA pieces per tile
@@ -424,9 +427,9 @@ __global__ void __launch_bounds__(kSThreads) sample_kernel(const ScreenArgs a) {
   }
   wait_vmcnt<0>();  // ordinary loads retired before the LDS-DMA ring starts
 
-  // tile sequence: the spread sample, or every tile of the split
-  auto phys = [&](int u) { return SAMPLE ? tb + (u * nt) / ns : tb + u; };
-  const int nv = SAMPLE ? ns : nt;
+  // tile sequence: the spread sample, ns of the split's nt tiles
+  auto sample_tile = [&](int u) { return tb + (u * nt) / ns; };
+  const int nv = ns;
 
   auto issue = [&](int tile, int stage) {
     const int64_t base = static_cast<int64_t>(tile) * kCTile;
@@ -471,61 +474,59 @@ __global__ void __launch_bounds__(kSThreads) sample_kernel(const ScreenArgs a) {
 
 #pragma unroll
   for (int s = 0; s < kStages - 1; ++s)
-    if (s < nv) issue(phys(s), s);
+    if (s < nv) issue(sample_tile(s), s);
   wait_tiles(min(nv, kStages - 1) - 1);
   __builtin_amdgcn_s_barrier();
 
-  if constexpr (SAMPLE) {
-  // ---- phase 1: sample tiles, bins only ------------------------------------
-    // bins: per lane and query set, 16 register positions x the 2 blocks of a tile
-    // (64 per query with the partner lane), running maxima of the sample.
-    float b0a[16], b0b[16], b1a[16], b1b[16];
-  #pragma unroll
-    for (int r = 0; r < 16; ++r) b0a[r] = b0b[r] = b1a[r] = b1b[r] = -INFINITY;
-    for (int u = 0; u < ns; ++u) {
-      if (u + kStages - 1 < nv) issue(phys(u + kStages - 1), (u + kStages - 1) % kStages);
-      const char* B = smem + (u % kStages) * TILE_BYTES;
-      const int64_t cbase = static_cast<int64_t>(phys(u)) * kCTile;
-  #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x16 c0 = {}, c1 = {};
-  #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          const bf16x8 af = frag(B, t, s);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bq0[s], c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bq1[s], c1, 0, 0, 0);
-        }
-        if (edge(cbase)) {
-          mask_pad(c0, cbase + 32 * t + 4 * h);
-          mask_pad(c1, cbase + 32 * t + 4 * h);
-        }
-        float (&x0)[16] = t == 0 ? b0a : b0b;  // static under the unroll
-        float (&x1)[16] = t == 0 ? b1a : b1b;
-  #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          x0[r] = __builtin_elementwise_maximum(x0[r], c0[r]);
-          x1[r] = __builtin_elementwise_maximum(x1[r], c1[r]);
-        }
+  // ---- sample tiles, bins only ----------------------------------------------
+  // bins: per lane and query set, 16 register positions x the 2 blocks of a tile
+  // (64 per query with the partner lane), running maxima of the sample.
+  float b0a[16], b0b[16], b1a[16], b1b[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) b0a[r] = b0b[r] = b1a[r] = b1b[r] = -INFINITY;
+  for (int u = 0; u < ns; ++u) {
+    if (u + kStages - 1 < nv) issue(sample_tile(u + kStages - 1), (u + kStages - 1) % kStages);
+    const char* B = smem + (u % kStages) * TILE_BYTES;
+    const int64_t cbase = static_cast<int64_t>(sample_tile(u)) * kCTile;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f32x16 c0 = {}, c1 = {};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const bf16x8 af = frag(B, t, s);
+        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bq0[s], c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bq1[s], c1, 0, 0, 0);
       }
-      advance(u);
+      if (edge(cbase)) {
+        mask_pad(c0, cbase + 32 * t + 4 * h);
+        mask_pad(c1, cbase + 32 * t + 4 * h);
+      }
+      float (&x0)[16] = t == 0 ? b0a : b0b;  // static under the unroll
+      float (&x1)[16] = t == 0 ? b1a : b1b;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        x0[r] = __builtin_elementwise_maximum(x0[r], c0[r]);
+        x1[r] = __builtin_elementwise_maximum(x1[r], c1[r]);
+      }
     }
-    if (a.bins) {  // pooled estimate: this lane's 32 of the query's 64 bins of this split
-      float* o0 = a.bins + (q0 * a.S + split) * 64 + 32 * h;
-      float* o1 = a.bins + (q1 * a.S + split) * 64 + 32 * h;
-  #pragma unroll
-      for (int r = 0; r < 16; r += 4) {
-        *reinterpret_cast<f32x4*>(o0 + r) = f32x4{b0a[r], b0a[r + 1], b0a[r + 2], b0a[r + 3]};
-        *reinterpret_cast<f32x4*>(o0 + 16 + r) = f32x4{b0b[r], b0b[r + 1], b0b[r + 2], b0b[r + 3]};
-        *reinterpret_cast<f32x4*>(o1 + r) = f32x4{b1a[r], b1a[r + 1], b1a[r + 2], b1a[r + 3]};
-        *reinterpret_cast<f32x4*>(o1 + 16 + r) = f32x4{b1b[r], b1b[r + 1], b1b[r + 2], b1b[r + 3]};
-      }
-    } else {
-      const float tq0 = ns > 0 ? bins_select(b0a, b0b, a.jsel) : -INFINITY;
-      const float tq1 = ns > 0 ? bins_select(b1a, b1b, a.jsel) : -INFINITY;
-      if (h == 0) {
-        a.tau_split[q0 * a.S + split] = tq0;
-        a.tau_split[q1 * a.S + split] = tq1;
-      }
+    advance(u);
+  }
+  if (a.bins) {  // pooled estimate: this lane's 32 of the query's 64 bins of this split
+    float* o0 = a.bins + (q0 * a.S + split) * 64 + 32 * h;
+    float* o1 = a.bins + (q1 * a.S + split) * 64 + 32 * h;
+#pragma unroll
+    for (int r = 0; r < 16; r += 4) {
+      *reinterpret_cast<f32x4*>(o0 + r) = f32x4{b0a[r], b0a[r + 1], b0a[r + 2], b0a[r + 3]};
+      *reinterpret_cast<f32x4*>(o0 + 16 + r) = f32x4{b0b[r], b0b[r + 1], b0b[r + 2], b0b[r + 3]};
+      *reinterpret_cast<f32x4*>(o1 + r) = f32x4{b1a[r], b1a[r + 1], b1a[r + 2], b1a[r + 3]};
+      *reinterpret_cast<f32x4*>(o1 + 16 + r) = f32x4{b1b[r], b1b[r + 1], b1b[r + 2], b1b[r + 3]};
+    }
+  } else {
+    const float tq0 = ns > 0 ? bins_select(b0a, b0b, a.jsel) : -INFINITY;
+    const float tq1 = ns > 0 ? bins_select(b1a, b1b, a.jsel) : -INFINITY;
+    if (h == 0) {
+      a.tau_split[q0 * a.S + split] = tq0;
+      a.tau_split[q1 * a.S + split] = tq1;
     }
   }
 }
@@ -658,11 +659,11 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
       a.buf + qblk * a.S * static_cast<int64_t>(a.cap), 0, 0x7fffffff, 0x00020000);
 
   // Filters nrows staged rows from the tail (one per lane) and appends their
-  // hits to the lists: per register r, the lanes whose score r beats their
-  // row's tau store it at their list's next slot.  Branch-free: 16 stores per
-  // flush, a lane without a hit in r addressing past the buffer resource's
-  // range (the store drops it; 4.53 -> 4.35 ms per 131k-query chunk against
-  // one branch per register).
+  // hits to the lists: a lane reserves its row's hit count in its query's
+  // list, then the wave stores in rounds, each lane its next hit (lowest
+  // register first), the score re-read from the staged row in LDS.  Rounds =
+  // the most hits in one row (usually 2, not 16); a lane with no hit left
+  // addresses past the buffer resource's range, and the store drops it.
   auto flush = [&](int nrows) {
     wsync();
     const float* row = srow + ((tail + lane) & (kStageRows - 1)) * kRowF;
@@ -674,9 +675,6 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
     const unsigned pcr = __float_as_uint(tg4[0]);
     const int ql = valid ? static_cast<int>(__float_as_uint(tg4[1])) : 0;
     const float tr = valid ? tau_l[ql] : INFINITY;
-#ifndef TT_SCAN_FLUSH_LOOP
-#define TT_SCAN_FLUSH_LOOP 1
-#endif
     unsigned hm = 0;  // the row's registers above tau
 #pragma unroll
     for (int r = 0; r < 16; ++r) hm |= (x[r >> 2][r & 3] > tr) ? (1u << r) : 0u;
@@ -689,43 +687,25 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
     }
     const unsigned lbase = static_cast<unsigned>((ql * a.S + split) * a.cap) * 8u;
     const int last = a.cap - 1;  // scratch slot: entries past it are dropped with the list
-    // branch-free: one store per register for the whole wave; a lane with no
-    // hit in it addresses past the resource's range, and the store drops it
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    if (TT_SCAN_FLUSH_LOOP) {
-      // one store per round for the whole wave, each lane storing its next
-      // hit (lowest register first: the same entries at the same slots as
-      // the per-register form), the score re-read from the staged row in
-      // LDS; rounds = the most hits in one row (usually 2), not 16
-      int rounds = 0;
-      while (__ballot(hm != 0u)) {
-        const int r = __builtin_ctz(hm | 0x10000u);  // 16 (the row's tag word) when none is left
-        const float v = row[r];
-        const u32x2 e = {__float_as_uint(v), pcr + static_cast<unsigned>((r & 3) + 8 * (r >> 2))};
-        const unsigned off = hm != 0u ? lbase + static_cast<unsigned>(min(pos, last)) * 8u : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b64(e, lists, off, 0, 0);
-        pos += hm != 0u ? 1 : 0;
-        hm &= hm - 1u;
-        ++rounds;
-      }
-      wc = __builtin_amdgcn_readfirstlane(wc + rounds);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = x[r >> 2][r & 3];
-        const bool keepit = v > tr;
-        const u32x2 e = {__float_as_uint(v), pcr + static_cast<unsigned>((r & 3) + 8 * (r >> 2))};
-        const unsigned off = keepit ? lbase + static_cast<unsigned>(min(pos, last)) * 8u : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b64(e, lists, off, 0, 0);
-        pos += keepit ? 1 : 0;
-      }
-      wc = __builtin_amdgcn_readfirstlane(wc + 16);
+    int rounds = 0;  // one store per round for the whole wave (they count in the vmcnt windows)
+    while (__ballot(hm != 0u)) {
+      const int r = __builtin_ctz(hm | 0x10000u);  // 16 (the row's tag word) when none is left
+      const float v = row[r];
+      const u32x2 e = {__float_as_uint(v), pcr + static_cast<unsigned>((r & 3) + 8 * (r >> 2))};
+      const unsigned off = hm != 0u ? lbase + static_cast<unsigned>(min(pos, last)) * 8u : 0x80000000u;
+      __builtin_amdgcn_raw_buffer_store_b64(e, lists, off, 0, 0);
+      pos += hm != 0u ? 1 : 0;
+      hm &= hm - 1u;
+      ++rounds;
     }
+    wc = __builtin_amdgcn_readfirstlane(wc + rounds);
     tail += nrows;
     wsync();
   };
-  // Stages the rows of this block's lanes whose max beats their tau.
-  auto stage = [&](const f32x16& c, bool hit, int ql, unsigned pc) {
+  // Stages the rows of this block's lanes whose max beats their tau (one
+  // query set: stage2's second round).
+  auto stage =[&](const f32x16& c, bool hit, int ql, unsigned pc) {
     const uint64_t m = __ballot(hit);
     if (m) {
       if (hit) {
@@ -743,9 +723,6 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
       if (head - tail >= kWave) flush(kWave);
     }
   };
-#ifndef TT_SCAN_PAIR_STAGE
-#define TT_SCAN_PAIR_STAGE 1
-#endif
   // Both query sets' rows of one block in ONE round of row stores: a lane
   // stages its set-0 row if that hits, else its set-1 row (selected in
   // registers); the lanes where both hit (~0.4 % of lanes) store their set-1
@@ -801,22 +778,14 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
   // has landed).
   bf16x8 f0[KS], f1[KS];
   f32x16 a0 = {}, a1 = {}, b0 = {}, b1 = {};
-#ifndef TT_SCAN_PRIO
-#define TT_SCAN_PRIO 0
-#endif
-  // 1: the younger half of the workgroup (waves 4-7) at priority 1 for the
-  // whole loop; 2: priority 1 around each MFMA cluster
-  if (TT_SCAN_PRIO == 1 && __builtin_amdgcn_readfirstlane(tid) >= kSThreads / 2) __builtin_amdgcn_s_setprio(1);
   auto mfmas = [&](const bf16x8 (&f)[KS], f32x16& x0, f32x16& x1) {
     x0 = f32x16{};
     x1 = f32x16{};
-    if (TT_SCAN_PRIO == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       x0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s], bq0[s], x0, 0, 0, 0);
       x1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s], bq1[s], x1, 0, 0, 0);
     }
-    if (TT_SCAN_PRIO == 2) __builtin_amdgcn_s_setprio(0);
   };
   // block (tile u, half t) held in (x0, x1): edge mask, candidate base, maxima
   struct Pend {
@@ -835,36 +804,26 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
     }
     return Pend{a.index_offset + static_cast<unsigned>(cb + 4 * h), max16(x0), max16(x1)};
   };
-#ifndef TT_SCAN_PROBE
-#define TT_SCAN_PROBE 0
-#endif
-  // probe builds (timing only, results unused): 1 = maxima without the
-  // ballot / staging branches, 2 = no filter work at all
+  // probe builds (TT_SCAN_PROBE; timing only, results unused): 1 = maxima
+  // without the ballot / staging branches, 2 = no filter work at all
   float probe_acc = 0.f;
   auto stage_pair = [&](const f32x16& x0, const f32x16& x1, const Pend& p) {
     if (TT_SCAN_PROBE == 1) {
       probe_acc = fmaxf(probe_acc, fmaxf(p.m0, p.m1));
     } else if (TT_SCAN_PROBE == 2) {
       probe_acc += x0[0] + x1[5];
-    } else if (TT_SCAN_PAIR_STAGE) {
-      stage2(x0, x1, p.m0 > tau0, p.m1 > tau1, p.pc);
     } else {
-      stage(x0, p.m0 > tau0, ql0, p.pc);
-      stage(x1, p.m1 > tau1, ql1, p.pc);
+      stage2(x0, x1, p.m0 > tau0, p.m1 > tau1, p.pc);
     }
   };
   if (nv > 0) load_frags(f0, smem, 0);
   for (int u = 0; u < nv; ++u) {
     // half A: MFMAs (u, 0) into A (F0 read during the previous half), then
-    // read F1 <- (u, 1), then filter (u - 1, 1) from B
-#ifndef TT_SCAN_LATE_B
-#define TT_SCAN_LATE_B 1
-#endif
-    // (TT_SCAN_LATE_B: filter B after the ring barrier, so the LDS drain the
-    // barrier needs covers the fragment reads only, not B's row stores)
+    // read F1 <- (u, 1), then filter (u - 1, 1) from B (after the ring
+    // barrier, so the LDS drain the barrier needs covers the fragment reads
+    // only, not B's row stores)
     mfmas(f0, a0, a1);
     load_frags(f1, smem + (u % kStages) * TILE_BYTES, 1);
-    if (!TT_SCAN_LATE_B && u > 0) stage_pair(b0, b1, prep(b0, b1, u - 1, 1));
     if (u + 1 < nv) {  // next tile: landed, every wave done with tile u, refill its stage
       wait_vmcnt_atmost((wa - da) + wb + wc);
       // compiler-visible wait + barrier: it then knows the fragment reads
@@ -882,23 +841,12 @@ __global__ void __launch_bounds__(kSThreads) scan_kernel(const ScreenArgs a) {
       }
       wc = dc;
     }
-    if (TT_SCAN_LATE_B && u > 0) stage_pair(b0, b1, prep(b0, b1, u - 1, 1));
+    if (u > 0) stage_pair(b0, b1, prep(b0, b1, u - 1, 1));
     // half B: MFMAs (u, 1) into B, then read F0 <- (u + 1, 0) (stale after the
     // last tile: unused), then filter (u, 0) from A
     mfmas(f1, b0, b1);
     load_frags(f0, smem + ((u + 1) % kStages) * TILE_BYTES, 0);
     stage_pair(a0, a1, prep(a0, a1, u, 0));
-#ifndef TT_SCAN_FLUSH_TILES
-#define TT_SCAN_FLUSH_TILES 0
-#endif
-    // optional: every wave flushes at the same tiles (so no wave flushing
-    // alone holds the others at the next ring barrier).  Off by default: a
-    // wave flushes when 64 rows are staged and at the end (1M x k=100: 44.7
-    // vs 45.2 ms with a flush every 4 tiles; every 8: much slower)
-#if TT_SCAN_FLUSH_TILES > 0
-    if (u % TT_SCAN_FLUSH_TILES == TT_SCAN_FLUSH_TILES - 1)
-      while (head > tail) flush(min(head - tail, kWave));
-#endif
   }
   if (nv > 0) stage_pair(b0, b1, prep(b0, b1, nv - 1, 1));
   if (TT_SCAN_PROBE && probe_acc == 12345.f) a.count[0] = -2;  // keeps the probe's work alive
@@ -1396,15 +1344,8 @@ __host__ __device__ inline size_t final_lds_bytes(int L, int P, int NW = 1) {
 // phase's loops over the waves (large k: long lists, many survivors, a
 // P-element sort), so a query's latency chain shrinks while its list stays
 // in LDS.
-#ifndef TT_FINAL_WPE
-#define TT_FINAL_WPE 0  // > 0: the finalize compiled for at least that many waves per SIMD
-#endif
 template <int NW>
-__global__ void __launch_bounds__(NW * kWave)
-#if TT_FINAL_WPE > 0
-    __attribute__((amdgpu_waves_per_eu(TT_FINAL_WPE)))
-#endif
-    finalize_kernel(const FinalArgs a) {
+__global__ void __launch_bounds__(NW * kWave) finalize_kernel(const FinalArgs a) {
   constexpr int NT = NW * kWave;
   extern __shared__ __attribute__((aligned(16))) char fsm[];
   float* qs = reinterpret_cast<float*>(fsm);  // query row (dim <= 128)
@@ -1532,31 +1473,6 @@ __global__ void __launch_bounds__(NW * kWave)
     if (!fail) {
       // certificate (below) is the only reason counted in stats[1]
       X = lb_of(order_key_float(r.prefix), m, rel);
-      // per-row bounds: the >= K entries at or above the K-th key prefix each
-      // score at least max(lb(s~), s~ - err_row) exactly, so X = the least of
-      // those lower bounds has >= K candidates at or above it (and is >= the
-      // relative / absolute form's lb(prefix))
-#ifndef TT_INDEX_ROW_X
-#define TT_INDEX_ROW_X 0
-#endif
-      if (TT_INDEX_ROW_X) {
-      unsigned xk = 0xFFFFFFFFu, unused = 0u;
-      auto visit = [&](float sv, unsigned iv) {
-        if (float_order_key(sv) >= r.prefix)
-          xk = min(xk, float_order_key(fmaxf(lb_of(sv, m, rel), sv - err_row(iv))));
-      };
-      if (staged) {
-        for (int i = t; i < ntot; i += NT) visit(sc[i], id[i]);
-      } else {
-        for (int j = 0; j < Ls.nseg; ++j) {
-          const int c = seg_count(Ls, q, j);
-          const uint2* e = seg_ptr(Ls, q, j);
-          for (int i = t; i < c; i += NT) visit(__uint_as_float(e[i].x), e[i].y);
-        }
-      }
-      group_minmax<NW>(xk, unused, wcnt);
-      if (xk != 0xFFFFFFFFu) X = fmaxf(X, order_key_float(xk));
-      }
       // certificate: every list kept all s~ > tau, and an unlisted row's
       // exact score is <= min(ub(tau), tau + the per-row bound at the index's
       // largest row norms) < X, which rules it out of the exact top-K (K
@@ -1830,6 +1746,9 @@ __global__ void __launch_bounds__(kFbWaves * kWave) fallback_kernel(const Fallba
 #ifndef TT_INDEX_R_ADD
 #define TT_INDEX_R_ADD 100.0
 #endif
+#ifndef TT_INDEX_LF  // least LDS list length of the finalize (entries per query)
+#define TT_INDEX_LF 1024
+#endif
 struct SearchPlan {
   int S, NS, jsel, cap, L, LF, P, k, parts;
   int pool;  // pooled estimate (> 1 sample splits): tau = the J-th largest of a query's Ss x 64 bins
@@ -1858,9 +1777,6 @@ SearchPlan plan_search(int64_t nq, int64_t n_rows, int k, int shards) {
   p.k = k;
   p.parts = 8192 / k < 1 ? 1 : (8192 / k > 64 ? 64 : 8192 / k);
   p.L = static_cast<int>(round_up(2 * static_cast<int64_t>(k) + 256, kWave));
-#ifndef TT_INDEX_LF
-#define TT_INDEX_LF 1024
-#endif
   p.LF = p.L > TT_INDEX_LF ? p.L : TT_INDEX_LF;  // finalize: a query's whole list (~3k + 100 entries) fits
   static const int nw_env = env_int("TT_FINAL_WAVES", 0), lf_env = env_int("TT_FINAL_LF", 0);
   p.NW = nw_env == 1 || nw_env == 2 || nw_env == 4 ? nw_env : (k >= 512 ? 4 : 1);

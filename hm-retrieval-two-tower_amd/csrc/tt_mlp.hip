@@ -60,10 +60,7 @@ namespace tt {
 namespace {
 
 constexpr int kMlpThreads = 256;
-#ifndef TT_MLP_BM
-#define TT_MLP_BM 64
-#endif
-constexpr int kMlpBM = TT_MLP_BM;  // rows per workgroup (32 or 64)
+constexpr int kMlpBM = 64;       // rows per workgroup
 constexpr int kMlpRB = kMlpBM / 32;  // 32-row MFMA blocks per wave
 constexpr int kMlpUQ = kMlpBM / 16;  // A rows per thread per stage
 constexpr int kMlpBK = 64;       // depth per A stage (4 MFMA k-steps)

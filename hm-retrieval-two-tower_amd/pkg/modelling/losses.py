@@ -74,12 +74,6 @@ def _tower_stream(device: torch.device) -> torch.cuda.Stream:
 # World-1 sharded step, interleaved pairs: 16384 rows 0.896-0.903 vs
 # 0.942-0.945 ms; 2048 rows (an 8-way split) 0.579-0.605 vs 0.562-0.599.
 GLOBAL_TOWER_STREAMS = int(os.environ.get("TT_GLOBAL_TOWER_STREAMS", "4096"))
-# The single-GPU step's towers on two streams (TT_TOWER_STREAMS=0: one).
-TOWER_STREAMS = int(os.environ.get("TT_TOWER_STREAMS", "1"))
-# The single-device step's loss summed by an extra workgroup of the loss
-# entry's last launch (tt_inbatch_softmax_xent_loss) instead of a tt_sum
-# launch after it (TT_LOSS_IN_COMBINE=0); the same value bit for bit.
-LOSS_IN_COMBINE = os.environ.get("TT_LOSS_IN_COMBINE", "1") == "1"
 # The global-negatives loss at one rank through the single-device entry
 # (TT_WORLD1_FUSED=0: the rows and columns entries, as at G > 1).
 WORLD1_FUSED = os.environ.get("TT_WORLD1_FUSED", "1") == "1"
@@ -168,7 +162,7 @@ class _TowersInBatchXent(torch.autograd.Function):
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
             return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower)
         main = torch.cuda.current_stream()
-        side = _tower_stream(qi.device) if TOWER_STREAMS else main
+        side = _tower_stream(qi.device)
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
         # (not under x3_scores(): that entry prepares its operands itself)
@@ -195,14 +189,12 @@ class _TowersInBatchXent(torch.autograd.Function):
             _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, loss_scale=scale, x3=True)
             ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
             return loss
-        if LOSS_IN_COMBINE:  # the loss sum inside the loss entry's last launch
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, ws=ws, prepped=ws is not None,
-                                                       loss_scale=scale)
-            ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
-            return loss
-        _, row_loss, dq, dc = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, ws=ws, prepped=ws is not None)
+        # the loss summed by an extra workgroup of the loss entry's last launch
+        # (tt_inbatch_softmax_xent_loss): no tt_sum launch after it
+        _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, ws=ws, prepped=ws is not None,
+                                                   loss_scale=scale)
         ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
-        return hip_ops.loss_sum(row_loss, scale)
+        return loss
 
     @staticmethod
     def backward(ctx, g):
@@ -215,7 +207,7 @@ class _TowersInBatchXent(torch.autograd.Function):
                     None, None, None, None, None, None)
         on_dx = ctx.on_dx
         main = torch.cuda.current_stream()
-        side = _tower_stream(dq.device) if TOWER_STREAMS else main
+        side = _tower_stream(dq.device)
         side.wait_stream(main)
         with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
             # this tower's updates (on_dx: the embedding update once its input

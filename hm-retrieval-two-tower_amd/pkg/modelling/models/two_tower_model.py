@@ -38,17 +38,10 @@ __all__ = ["TwoTowerModel", "GraphedTrainStep", "LOGQ_KEY"]
 # Optional batch entry carrying per-example log p(candidate) computed from raw
 # ids at encoding time (exact even for ids outside a truncated vocab).
 LOGQ_KEY = "__logq__"
-# where the embedding update's id sort may start: as soon as the batch's ids
-# are gathered ("gather", default: 6 interleaved A/B pairs on the C3 step,
-# 6.6 us/step faster than "loss" on average) or after the whole forward ("loss");
-# either way it is captured after the backward, so its launch follows them
-SORT_AFTER = os.environ.get("TT_SORT_AFTER", "gather")
 # each tower's dense (MLP) Adagrad step issued inside the backward on that
 # tower's stream the moment its weight gradient exists, instead of after the
 # join (the embedding update stays one call after the backward)
 DENSE_EARLY = os.environ.get("TT_DENSE_EARLY", "1") == "1"
-# fused apply: the per-tower id sorts issued right after the gather
-FUSED_SORT_EARLY = os.environ.get("TT_FUSED_SORT_EARLY", "1") == "1"
 # with DENSE_EARLY: each layer's Adagrad step applied by its weight-gradient
 # launches (tt_mlp_wgrad_adagrad: the partial-sum launch updates the layer)
 # instead of one dense_adagrad launch per tower after its backward
@@ -180,26 +173,15 @@ class TwoTowerModel(AbstractKerasModel):
                     pack = []
             qi, ci = InputLayer.gather_many([self.query_tower.input_layer, self.candidate_tower.input_layer], [q, c],
                                             extra=[call] if call is not None else (), pack_jobs=pack or None)
-            self._sort_issued = False
             if training and qi.is_cuda:
                 # the embedding update's id sort needs only these ids
                 self._ids_ready = torch.cuda.Event()
                 self._ids_ready.record()
-                if (SORT_AFTER == "early" and getattr(self, "_in_train_step", False)
-                        and hasattr(self.optimizer, "prepare")
-                        and getattr(self, "_on_tower", None) in (None, self._apply_dense_tower)):
-                    # issued (and so captured) right here: a graph replays nodes
-                    # in capture order, so a sort captured after the backward
-                    # starts after it even when only the ids gate it
-                    self.optimizer.prepare(self.towers, after=self._ids_ready)
-                    self._sort_issued = True
-                if (FUSED_SORT_EARLY and getattr(self, "_in_train_step", False)
-                        and getattr(self, "_on_tower", None) == self._apply_tower):
-                    # fused apply: the per-tower id sorts captured right after the
-                    # gather (their only input), so they overlap the forward
-                    # instead of landing in front of the backward
+                if getattr(self, "_on_tower", None) == self._apply_tower:
+                    # fused apply (train_step): the per-tower id sorts captured
+                    # right after the gather (their only input), so they overlap
+                    # the forward instead of landing in front of the backward
                     self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
-                    self._sort_issued = True
             logq = call[1].view(-1) if call is not None else self.candidate_logq(x)
             return self.tower_loss(qi, ci, logq)
 
@@ -260,28 +242,17 @@ class TwoTowerModel(AbstractKerasModel):
         # fused: each tower's embedding update the moment its input gradient
         # exists (the weight gradients follow it on that tower's stream)
         self._on_dx = self._apply_tower_sparse if (fused and _tower_mod.IGRAD_FIRST) else None
-        self._in_train_step = True
         try:
-            loss = self.compute_loss(data, training=True)
+            loss = self.compute_loss(data, training=True)  # fused: issues the per-tower id sorts
         finally:
             self._on_tower = None
             self._on_dx = None
-            self._in_train_step = False
         fwd_done = None
-        if fused and not getattr(self, "_sort_issued", False):
-            # one id sort per tower on a side stream, before the backward needs it
-            self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
-        elif hasattr(self.optimizer, "prepare") and loss.is_cuda and not getattr(self, "_sort_issued", False):
-            if SORT_AFTER == "gather" and getattr(self, "_ids_ready", None) is not None:
-                fwd_done = self._ids_ready
-            else:
-                fwd_done = torch.cuda.Event()
-                fwd_done.record()
-        if fwd_done is not None and SORT_AFTER == "mid":
-            # captured between the forward and the backward: launched before the
-            # backward's nodes, ordered after the forward only
-            self.optimizer.prepare(self.towers, after=fwd_done)
-            fwd_done = None
+        if not fused and hasattr(self.optimizer, "prepare") and loss.is_cuda:
+            # the id sort waits for the gather only (compute_loss recorded the
+            # event), not the whole forward: 6.6 us/step on the C3 step over 6
+            # interleaved pairs
+            fwd_done = self._ids_ready
         for t in self.towers:
             t.dense.flat.grad = None
         if getattr(self, "_one", None) is None or self._one.device != loss.device:
