@@ -434,28 +434,55 @@ __global__ void __launch_bounds__(1024) mlp_colsum_kernel(const float* __restric
 //   layer's output gradient, optionally Gm = (gmask > 0) ? G * s : 0 — the
 //   ReluGrad of the layer's own relu folded into the load)
 // The output [Ka + 1, N] is exactly the flat parameter layout (kernel rows
-// then the bias row).  Split-K over the batch: grid = S splits x 64 x 64
-// output tiles; each workgroup reduces its split's rows for one tile into
-// its split's partial [Ka + 1, N], and mlp_sum_parts_kernel adds the
-// partials in split order (deterministic).  The tiles of one split sit on
-// one XCD (blockIdx % 8 picks the XCD), so the split's rows that its tiles
-// all stage come from that XCD's L2.
-// Both MFMA operands need 8 consecutive BATCH rows per lane; the staged
-// 32-row stages are written ROW-major (as loaded: each thread converts 8
-// consecutive columns of one row to bf16 hi / lo and stores 16 B per plane)
-// and the fragments are read with the hardware transposing read
-// ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group, delivered
-// column-major).  Rows are 192 B apart (128 B of data): the 4 rows x 2 groups
-// of a 32-lane half then start at banks 48q + 8g mod 64, all distinct.
-// 4 waves; wave w owns the 32 x 32 block (w & 1, w >> 1) of the tile;
-// bf16x3 (a_lo b_hi + a_hi b_lo + a_hi b_hi), fp32 accumulation.
+// then the bias row).
+//
+// One kernel template, mlp_wgrad_block<MASK, WI, WJ>, for every output tile
+// of 64 WI x 64 WJ (64 x 64, 128 x 64, 64 x 128, 128 x 128; wgrad_tile() below
+// picks, DESIGN section 9 has what each measured).
+// Split-K over the batch: grid = S splits x output tiles; each workgroup
+// reduces its split's rows for one tile into its split's partial
+// [Ka + 1, N], and mlp_sum_parts_kernel adds the partials in split order
+// (deterministic).  The tiles of one split sit on one XCD (blockIdx % 8
+// picks the XCD), so the split's rows that its tiles all stage come from
+// that XCD's L2.
+// Stage: both MFMA operands need 8 consecutive BATCH rows per lane; the
+// 32-row stages (planes A hi, A lo, G hi, G lo) are written ROW-major (as
+// loaded: each thread converts 8 consecutive columns of one row to bf16
+// hi / lo and stores 16 B per plane) and the fragments are read with the
+// hardware transposing read ds_read_b64_tr_b16 (4 rows x 16 columns per
+// 16-lane group, delivered column-major).  A 64-column plane has rows 192 B
+// apart (128 B of data), a 128-column one 320 B (256 B of data).  Banks: a
+// transposing read serves a 32-lane half per cycle over 64 banks; its 4 rows
+// x 2 16-lane groups are 8 banks wide each and start at bank 48 q + 8 g
+// (mod 64) for the 192-B pitch and 80 q + 8 g = 16 q + 8 g for 320 B past
+// the fragment's first column: eight disjoint ranges that cover the 64 banks.
+// The stash stores 16 B per lane with the 8 (16) lanes of a row writing its
+// 128 (256) contiguous bytes: every 8-lane group of a ds_write_b128 covers
+// the 32 store banks once.
+// 4 waves; wave w owns the quadrant (w & 1, w >> 1) of the tile; bf16x3
+// (a_lo b_hi, then a_hi b_lo, then a_hi b_hi), fp32 accumulation.
+//
+// What WI and WJ change.  A wave's quadrant is WI x WJ MFMA blocks of
+// 32 x 32, so per k-step it reads WI + WJ fragments per plane and issues
+// 3 WI WJ MFMAs (3 per 8 transposing reads at 64 x 64, 12 per 16 at
+// 128 x 128); each A element is re-read and split by N / (64 WJ) column
+// tiles and each G element by (Ka + 1) / (64 WI) row tiles.  The splits, the
+// 16-row k-steps from the split's first row, the k -> lane mapping of the
+// fragments and the order of the three products do not depend on WI, WJ, so
+// every output element sums the same terms in the same order: all tiles are
+// bit-identical.  LDS, double-buffered: 48 KiB at 64 x 64, 64 KiB for the two
+// half-wide shapes, 80 KiB at 128 x 128 (40 KiB per stage); at most 256
+// registers (2 waves per SIMD), so at least two workgroups share a CU — the
+// two towers' launches run side by side.  Two stages of loads are in flight
+// for every tile (three do not fit the registers beside the accumulators:
+// the 128 x 128 build spilled ~100 registers), with the stash of the next
+// stage under the MFMAs of this one.  The splits are not the tile's to
+// change, so a wide tile has 2-4 x fewer workgroups (96-256 at the C3
+// shapes, one per CU at most): what it saves in staged bytes and conversions
+// it partly pays back in exposed load latency.
 constexpr int kWgThreads = 256;
-constexpr int kWgTile = 64;       // output tile: 64 rows of [A | 1]^T x 64 columns of Gm
+constexpr int kWgTile = 64;       // tile unit: 64 rows of [A | 1]^T x 64 columns of Gm
 constexpr int kWgBK = 32;         // batch rows per stage (2 MFMA k-steps)
-constexpr int kWgRowB = 192;      // LDS bytes per staged row
-constexpr int kWgPlaneB = kWgBK * kWgRowB;       // 6 KiB
-constexpr int kWgStageB = 4 * kWgPlaneB;         // A hi, A lo, G hi, G lo: 24 KiB
-constexpr int kWgDepth = 3;       // stages of global loads in flight
 
 struct WgradArgs {
   const float* A;
@@ -475,211 +502,6 @@ struct WgradArgs {
 typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) wg_bf16x4 lds_bf16x4_t;
 
-// Workgroup b of one problem; wsm holds 2 * kWgStageB bytes.
-template <bool MASK>
-__device__ __forceinline__ void mlp_wgrad_block(const WgradArgs& a, const int b, char* wsm) {
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const int lane = lane_id();
-  // b -> (split, tile); the tiles of a split on one XCD when S % 8 == 0
-  const int tiles = a.TI * a.TJ;
-  int split, tile;
-  {
-    if (a.S % 8 == 0) {
-      const int q = b >> 3;
-      tile = q % tiles;
-      split = (q / tiles) * 8 + (b & 7);
-    } else {
-      tile = b % tiles;
-      split = b / tiles;
-    }
-  }
-  const int i0 = (tile / a.TJ) * kWgTile;  // first [A | 1] column (= output row)
-  const int j0 = (tile % a.TJ) * kWgTile;  // first Gm column
-  const int64_t r0 = static_cast<int64_t>(split) * a.rows_per_split;
-  int64_t r1 = r0 + a.rows_per_split;
-  if (r1 > a.M) r1 = a.M;
-  // a split starting past M (rows_per_split is rounded up to whole stages)
-  // has no rows: its descriptors get 0 bytes, so the prologue's loads return
-  // zeros instead of reading past the operands
-  if (r1 < r0) r1 = r0;
-  const int nstage = r1 > r0 ? static_cast<int>((r1 - r0 + kWgBK - 1) / kWgBK) : 0;
-  const float s = a.scale ? *a.scale : 1.0f;
-
-  // loader: thread t stages row t / 8 of a stage, columns 8 (t % 8) .. + 7 of
-  // both operand tiles; range-checked buffer loads (rows past the split read 0)
-  const int lrow = tid >> 3, lcol = (tid & 7) * 8;
-  const __amdgpu_buffer_rsrc_t dA = mlp_desc(a.A + r0 * a.lda, static_cast<uint64_t>(r1 - r0) * a.lda * 4);
-  const __amdgpu_buffer_rsrc_t dG = mlp_desc(a.G + r0 * a.ldg, static_cast<uint64_t>(r1 - r0) * a.ldg * 4);
-  const __amdgpu_buffer_rsrc_t dM =
-      mlp_desc(MASK ? a.gmask + r0 * a.ldgm : a.G, static_cast<uint64_t>(r1 - r0) * (MASK ? a.ldgm : a.ldg) * 4);
-  const unsigned lda4 = static_cast<unsigned>(a.lda) * 4, ldg4 = static_cast<unsigned>(a.ldg) * 4,
-                 ldm4 = static_cast<unsigned>(MASK ? a.ldgm : a.ldg) * 4;
-  // columns past Ka (A) / N (Gm) are zeroed after the load (their loads read
-  // on into the row's padding or the next row, or 0 past the split)
-  const int ca = i0 + lcol, cg = j0 + lcol;
-  const unsigned oa = lrow * lda4 + static_cast<unsigned>(ca) * 4;
-  const unsigned og = lrow * ldg4 + static_cast<unsigned>(cg) * 4;
-  const unsigned om = lrow * ldm4 + static_cast<unsigned>(cg) * 4;
-  f32x4 va[kWgDepth][2], vg[kWgDepth][2], vm[kWgDepth][MASK ? 2 : 1];
-  auto fetch = [&](int st, auto slot_c) {
-    constexpr int SL = decltype(slot_c)::value;
-    const unsigned sa = static_cast<unsigned>(st * kWgBK) * lda4, sg = static_cast<unsigned>(st * kWgBK) * ldg4,
-                   sm = static_cast<unsigned>(st * kWgBK) * ldm4;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      va[SL][e] = mlp_load4s(dA, oa + 16 * e, sa);
-      vg[SL][e] = mlp_load4s(dG, og + 16 * e, sg);
-      if constexpr (MASK) vm[SL][e] = mlp_load4s(dM, om + 16 * e, sm);
-    }
-  };
-  // 8 values -> 16 B of hi and 16 B of lo at (plane pair, this thread's row, columns)
-  auto put8 = [&](char* base, const float (&x)[8]) {
-    unsigned hw[4], lw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const unsigned h0 = bf16_bits(x[2 * e]), h1 = bf16_bits(x[2 * e + 1]);
-      const unsigned l0 = bf16_bits(x[2 * e] - bf16_val(h0)), l1 = bf16_bits(x[2 * e + 1] - bf16_val(h1));
-      hw[e] = h0 | (h1 << 16);
-      lw[e] = l0 | (l1 << 16);
-    }
-    char* p = base + lrow * kWgRowB + lcol * 2;
-    *reinterpret_cast<u32x4*>(p) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-    *reinterpret_cast<u32x4*>(p + kWgPlaneB) = u32x4{lw[0], lw[1], lw[2], lw[3]};
-  };
-  auto stash = [&](int st, int buf, auto slot_c) {
-    constexpr int SL = decltype(slot_c)::value;
-    char* base = wsm + buf * kWgStageB;
-    const bool live = r0 + static_cast<int64_t>(st) * kWgBK + lrow < r1;
-    float x[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {  // [A | 1]: the ones column is the bias row of the output
-      const int col = ca + e;
-      x[e] = col < a.Ka ? va[SL][e >> 2][e & 3] : ((col == a.Ka && live) ? 1.0f : 0.0f);
-    }
-    put8(base, x);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int col = cg + e;
-      float v = col < a.N ? vg[SL][e >> 2][e & 3] : 0.0f;
-      if constexpr (MASK) v = vm[SL][e >> 2][e & 3] > 0.0f ? v * s : 0.0f;
-      x[e] = v;
-    }
-    put8(base + 2 * kWgPlaneB, x);
-  };
-
-  // fragments: 16-lane group g -> MFMA rows / columns 16 (g & 1) .. + 15 of
-  // the wave's 32-block, batch rows 8 (g >> 1) .. + 7 of the k-step; lane
-  // 4q + p of the group addresses row q, columns 4p .. 4p + 3
-  const int ib = wave & 1, jb = wave >> 1;
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int frow = 8 * (g >> 1) + q;
-  const int fa = frow * kWgRowB + (32 * ib + 16 * (g & 1) + 4 * p) * 2;
-  const int fg = 2 * kWgPlaneB + frow * kWgRowB + (32 * jb + 16 * (g & 1) + 4 * p) * 2;
-  auto frag = [&](const char* base, int off) {
-    const wg_bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(base + off));
-    const wg_bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(base + off + 4 * kWgRowB));
-    return __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
-  f32x16 acc = {};
-  auto compute = [&](int buf) {
-    const char* base = wsm + buf * kWgStageB;
-#pragma unroll
-    for (int ks = 0; ks < kWgBK / 16; ++ks) {
-      const int ko = ks * 16 * kWgRowB;
-      const bf16x8 ah = frag(base, fa + ko), al = frag(base + kWgPlaneB, fa + ko);
-      const bf16x8 gh = frag(base, fg + ko), gl = frag(base + kWgPlaneB, fg + ko);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh, acc, 0, 0, 0);
-    }
-  };
-
-  // pipeline: kWgDepth stages of loads in flight; stage st is stashed into
-  // buffer st % 2 right after its loads land, one barrier per stage (a wave
-  // passes it only after computing stage st - 1 from the other buffer)
-  static_assert(kWgDepth == 3, "the stage loop below is unrolled 3x");
-  fetch(0, std::integral_constant<int, 0>());  // issued in stage order (the waits count on it)
-  __builtin_amdgcn_sched_barrier(0);
-  fetch(1, std::integral_constant<int, 1>());
-  __builtin_amdgcn_sched_barrier(0);
-  fetch(2, std::integral_constant<int, 2>());
-  auto step = [&](int st, auto slot_c) {
-    // nothing crosses a step boundary: the scheduler would otherwise hoist the
-    // later steps' conversions to the loop top and wait for every load there
-    __builtin_amdgcn_sched_barrier(0);
-    stash(st, st & 1, slot_c);
-    __builtin_amdgcn_sched_barrier(0);
-    fetch(st + kWgDepth, slot_c);  // past the split: zeros, unused
-    __builtin_amdgcn_sched_barrier(0);
-    lds_barrier();
-    compute(st & 1);
-  };
-  // branch-free body (stages past the split stage zeros, which add nothing),
-  // so the compiler's vmcnt waits stay exact across the stages in flight
-  for (int st = 0; st < nstage; st += 3) {
-    step(st, std::integral_constant<int, 0>());
-    step(st + 1, std::integral_constant<int, 1>());
-    step(st + 2, std::integral_constant<int, 2>());
-  }
-
-  // this block of the split's partial: lane (l32, h), register r -> row
-  // 32 ib + (r & 3) + 8 (r >> 2) + 4 h, column 32 jb + l32
-  const int rows_out = a.Ka + 1;
-  float* P = a.parts + static_cast<int64_t>(split) * rows_out * a.N;
-  const int n = j0 + 32 * jb + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = i0 + 32 * ib + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (n < a.N && row < rows_out) P[static_cast<int64_t>(row) * a.N + n] = acc[r];
-  }
-}
-
-template <bool MASK>
-__global__ void __launch_bounds__(kWgThreads) mlp_wgrad_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgStageB];
-  mlp_wgrad_block<MASK>(a, blockIdx.x, wsm);
-}
-
-// Two problems in one launch: blocks [0, split) are a0's (split % 8 == 0
-// keeps the second problem's split -> XCD mapping).
-template <bool MASK>
-__global__ void __launch_bounds__(kWgThreads) mlp_wgrad_pair_kernel(const WgradArgs a0, const WgradArgs a1,
-                                                                    const int split) {
-  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgStageB];
-  const int b = blockIdx.x;
-  if (b < split) mlp_wgrad_block<MASK>(a0, b, wsm);
-  else mlp_wgrad_block<MASK>(a1, b - split, wsm);
-}
-
-// The wide-tile form of the same product (the default; TT_WGRAD_TILE=64 keeps
-// the kernel above as the reference path).  One workgroup owns a
-// 64 WI x 64 WJ output tile (128 x 64, 64 x 128 or 128 x 128; wgrad_tile()
-// below picks, DESIGN section 9 has what each measured), wave w the quadrant
-// (w & 1, w >> 1) of it: WI x WJ MFMA blocks, so per k-step a wave reads
-// WI + WJ fragments per plane and issues 3 WI WJ MFMAs (12 per 16 transposing
-// reads, where the 64 x 64 tile issues 3 per 8), each A element is re-read and
-// split by N / (64 WJ) column tiles instead of N / 64 and each G element by
-// (Ka + 1) / (64 WI) row tiles.  The splits, the 16-row k-steps from the
-// split's first row, the k -> lane mapping of the fragments and the order of
-// the three products are those of the 64 x 64 kernel, so every output element
-// sums the same terms in the same order: the two are bit-identical.
-// Stage: 32 rows, planes A hi, A lo, G hi, G lo; a 128-column plane has rows
-// 320 B apart (256 B of data), a 64-column one 192 B.  Banks: a transposing
-// read serves a 32-lane half per cycle over 64 banks; its 4 rows x 2 16-lane
-// groups are 8 banks wide each and start at bank 80 q + 8 g = 16 q + 8 g
-// (mod 64) for the 320-B pitch (48 q + 8 g for 192 B) past the fragment's
-// first column: eight disjoint ranges that cover the 64 banks.  The stash
-// stores 16 B per lane with the 16 (8) lanes of a row writing its 256 (128)
-// contiguous bytes: every 8-lane group of a ds_write_b128 covers the 32 store
-// banks once.  128 x 128: 40 KiB per stage, 80 KiB double-buffered (64 KiB for
-// the two half-wide shapes), and at most 256 registers (2 waves per SIMD), so
-// two workgroups share a CU — the two towers' launches run side by side.  Two
-// stages of loads are in flight (three do not fit the registers beside the
-// accumulators: the 128 x 128 build spilled ~100 registers).  The splits are
-// not the tile's to change, so a wide tile has 2-4 x fewer workgroups (96-256
-// at the C3 shapes, one per CU at most): what it saves in staged bytes and
-// conversions it partly pays back in exposed load latency.
 constexpr int wg_pitch(int w) { return w == 2 ? 320 : 192; }
 typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
@@ -687,20 +509,21 @@ __device__ __forceinline__ unsigned wg_pack2(float lo, float hi) {  // bf16(lo) 
   return __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{lo, hi}, wg_bf16x2));
 }
 template <int WI, int WJ>
-constexpr int kWgWideStageB = 2 * kWgBK * (wg_pitch(WI) + wg_pitch(WJ));
+constexpr int kWgStageB = 2 * kWgBK * (wg_pitch(WI) + wg_pitch(WJ));
 
+// Workgroup b of one problem; wsm holds 2 * kWgStageB<WI, WJ> bytes.
 template <bool MASK, int WI, int WJ>
-__device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const int b, char* wsm) {
+__device__ __forceinline__ void mlp_wgrad_block(const WgradArgs& a, const int b, char* wsm) {
   constexpr int TA = 64 * WI, TG = 64 * WJ;
   constexpr int PA = wg_pitch(WI), PG = wg_pitch(WJ);
   constexpr int PLA = kWgBK * PA, PLG = kWgBK * PG;  // plane bytes
-  constexpr int STAGE = kWgWideStageB<WI, WJ>;
+  constexpr int STAGE = kWgStageB<WI, WJ>;
   constexpr int RA = kWgBK / WI, RG = kWgBK / WJ;  // rows per loader pass
   constexpr int D = 2;                             // stages of global loads in flight
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int lane = lane_id();
-  // b -> (split, tile) as in mlp_wgrad_block
+  // b -> (split, tile); the tiles of a split on one XCD when S % 8 == 0
   const int tiles = a.TI * a.TJ;
   int split, tile;
   if (a.S % 8 == 0) {
@@ -716,12 +539,16 @@ __device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const i
   const int64_t r0 = static_cast<int64_t>(split) * a.rows_per_split;
   int64_t r1 = r0 + a.rows_per_split;
   if (r1 > a.M) r1 = a.M;
-  if (r1 < r0) r1 = r0;  // an empty split: 0-byte descriptors, every load reads 0
+  // a split starting past M (rows_per_split is rounded up to whole stages)
+  // has no rows: its descriptors get 0 bytes, so every load returns zeros
+  // instead of reading past the operands
+  if (r1 < r0) r1 = r0;
   const int nstage = r1 > r0 ? static_cast<int>((r1 - r0 + kWgBK - 1) / kWgBK) : 0;
   const float s = a.scale ? *a.scale : 1.0f;
 
   // loader: an operand tile of 64 W columns has 8 W lanes per row (8 columns
-  // each) and is staged in W passes of 32 / W rows
+  // each) and is staged in W passes of 32 / W rows; range-checked buffer loads
+  // (rows past the split read 0)
   const int rowa = tid / (8 * WI), cola = (tid % (8 * WI)) * 8;
   const int rowg = tid / (8 * WJ), colg = (tid % (8 * WJ)) * 8;
   const __amdgpu_buffer_rsrc_t dA = mlp_desc(a.A + r0 * a.lda, static_cast<uint64_t>(r1 - r0) * a.lda * 4);
@@ -768,7 +595,9 @@ __device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const i
     *reinterpret_cast<u32x4*>(p + plane) = u32x4{lw[0], lw[1], lw[2], lw[3]};
   };
   // EDGE: the tile reaches past column Ka - 1 of A (the ones column, padding)
-  // or past column N - 1 of Gm; an interior tile stages what it loaded
+  // or past column N - 1 of Gm: those columns are set after the load (their
+  // loads read on into the row's padding or the next row, or 0 past the
+  // split); an interior tile stages what it loaded
   auto stash = [&](int st, int buf, auto slot_c, auto edge_c) {
     constexpr int SL = decltype(slot_c)::value;
     constexpr bool EDGE = decltype(edge_c)::value;
@@ -800,8 +629,9 @@ __device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const i
     }
   };
 
-  // fragments as in mlp_wgrad_block: 16-lane group g -> rows / columns
-  // 16 (g & 1) .. + 15 of a 32-block, batch rows 8 (g >> 1) .. + 7 of the k-step
+  // fragments: 16-lane group g -> MFMA rows / columns 16 (g & 1) .. + 15 of
+  // a 32-block, batch rows 8 (g >> 1) .. + 7 of the k-step; lane 4q + p4 of
+  // the group addresses row q, columns 4 p4 .. 4 p4 + 3
   const int ib = wave & 1, jb = wave >> 1;
   const int g = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
   const int frow = 8 * (g >> 1) + q;
@@ -869,10 +699,15 @@ __device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const i
       step(st + 1, std::integral_constant<int, 0>());
     }
   };
-  // workgroup-uniform: a scalar branch, every lane stays active for the transposing reads
+  // branch-free loop bodies (stages past the split stage zeros, which add
+  // nothing), so the compiler's vmcnt waits stay exact across the stages in
+  // flight; the edge test is workgroup-uniform: a scalar branch, every lane
+  // stays active for the transposing reads
   if (i0 + TA > a.Ka || j0 + TG > a.N) pipeline(std::true_type());
   else pipeline(std::false_type());
 
+  // block (bi, bj) of the split's partial: lane (l32, h), register r -> row
+  // 32 (WI ib + bi) + (r & 3) + 8 (r >> 2) + 4 h, column 32 (WJ jb + bj) + l32
   const int rows_out = a.Ka + 1;
   float* P = a.parts + static_cast<int64_t>(split) * rows_out * a.N;
 #pragma unroll
@@ -889,18 +724,20 @@ __device__ __forceinline__ void mlp_wgrad_wide_block(const WgradArgs& a, const i
 }
 
 template <bool MASK, int WI, int WJ>
-__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_wide_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgWideStageB<WI, WJ>];
-  mlp_wgrad_wide_block<MASK, WI, WJ>(a, blockIdx.x, wsm);
+__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_kernel(const WgradArgs a) {
+  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgStageB<WI, WJ>];
+  mlp_wgrad_block<MASK, WI, WJ>(a, blockIdx.x, wsm);
 }
 
+// Two problems in one launch: blocks [0, split) are a0's (split % 8 == 0
+// keeps the second problem's split -> XCD mapping).
 template <bool MASK, int WI, int WJ>
-__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_wide_pair_kernel(const WgradArgs a0, const WgradArgs a1,
+__global__ void __launch_bounds__(kWgThreads, 2) mlp_wgrad_pair_kernel(const WgradArgs a0, const WgradArgs a1,
                                                                             const int split) {
-  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgWideStageB<WI, WJ>];
+  __shared__ __attribute__((aligned(16))) char wsm[2 * kWgStageB<WI, WJ>];
   const int b = blockIdx.x;
-  if (b < split) mlp_wgrad_wide_block<MASK, WI, WJ>(a0, b, wsm);
-  else mlp_wgrad_wide_block<MASK, WI, WJ>(a1, b - split, wsm);
+  if (b < split) mlp_wgrad_block<MASK, WI, WJ>(a0, b, wsm);
+  else mlp_wgrad_block<MASK, WI, WJ>(a1, b - split, wsm);
 }
 
 // out[e] = sum over splits of parts[sp][e] (deterministic): a block covers 64
@@ -1210,10 +1047,10 @@ extern "C" size_t tt_mlp_wgrad_workspace_size(int64_t M, int32_t Ka, int32_t N) 
 
 // The output tile of the weight-gradient launches, in 64-wide units per side
 // ([A | 1] columns x Gm columns).  TT_WGRAD_TILE (read at every call, so one
-// process can run every form): unset = the wide kernel, 128 x 64 for a masked
-// problem (Gm and its mask are the doubled stream: half as many row tiles
-// re-read them) and 64 x 128 otherwise; 128 = 128 x 128; 128x64 / 64x128 =
-// that shape for every problem; 64 = the 64 x 64 reference kernel.
+// process can run every form): unset = 128 x 64 for a masked problem (Gm and
+// its mask are the doubled stream: half as many row tiles re-read them) and
+// 64 x 128 otherwise; 128 = 128 x 128; 128x64 / 64x128 / 64 = that shape
+// (64: 64 x 64) for every problem.
 struct WgradTile {
   int wi, wj;
 };
@@ -1265,26 +1102,28 @@ static int wgrad_setup(const char* fn, const float* A, int64_t lda, const float*
   return TT_OK;
 }
 
-template <int WI, int WJ>
-static void launch_wgrad_wide(const WgradArgs& a, dim3 grid, hipStream_t st) {
-  if (a.gmask) hipLaunchKernelGGL((mlp_wgrad_wide_kernel<true, WI, WJ>), grid, dim3(kWgThreads), 0, st, a);
-  else hipLaunchKernelGGL((mlp_wgrad_wide_kernel<false, WI, WJ>), grid, dim3(kWgThreads), 0, st, a);
+// (tile, masked) -> the kernels' <MASK, WI, WJ>: calls f(mask, wi, wj) with
+// the three as integral constants (a validated tile: wi, wj in {1, 2})
+template <class F>
+static void wgrad_dispatch(const WgradTile t, const bool masked, F&& f) {
+  using one = std::integral_constant<int, 1>;
+  using two = std::integral_constant<int, 2>;
+  auto tile = [&](auto mask) {
+    if (t.wi == 2 && t.wj == 2) f(mask, two(), two());
+    else if (t.wi == 2) f(mask, two(), one());
+    else if (t.wj == 2) f(mask, one(), two());
+    else f(mask, one(), one());
+  };
+  if (masked) tile(std::true_type());
+  else tile(std::false_type());
 }
 
 static void launch_wgrad(const WgradArgs& a, const WgradTile t, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(a.S * a.TI * a.TJ));
-  if (t.wi == 2 && t.wj == 2) launch_wgrad_wide<2, 2>(a, grid, st);
-  else if (t.wi == 2) launch_wgrad_wide<2, 1>(a, grid, st);
-  else if (t.wj == 2) launch_wgrad_wide<1, 2>(a, grid, st);
-  else if (a.gmask) hipLaunchKernelGGL((mlp_wgrad_kernel<true>), grid, dim3(kWgThreads), 0, st, a);
-  else hipLaunchKernelGGL((mlp_wgrad_kernel<false>), grid, dim3(kWgThreads), 0, st, a);
-}
-
-template <int WI, int WJ>
-static void launch_wgrad_wide_pair(const WgradArgs& a0, const WgradArgs& a1, int nb0, dim3 grid, hipStream_t st) {
-  if (a0.gmask)
-    hipLaunchKernelGGL((mlp_wgrad_wide_pair_kernel<true, WI, WJ>), grid, dim3(kWgThreads), 0, st, a0, a1, nb0);
-  else hipLaunchKernelGGL((mlp_wgrad_wide_pair_kernel<false, WI, WJ>), grid, dim3(kWgThreads), 0, st, a0, a1, nb0);
+  wgrad_dispatch(t, a.gmask != nullptr, [&](auto mask, auto wi, auto wj) {
+    hipLaunchKernelGGL((mlp_wgrad_kernel<decltype(mask)::value, decltype(wi)::value, decltype(wj)::value>), grid,
+                       dim3(kWgThreads), 0, st, a);
+  });
 }
 
 namespace {
@@ -1364,11 +1203,10 @@ extern "C" int tt_mlp_wgrad_pair(const tt_mlp_wgrad_problem* p, void* workspace,
     launch_wgrad(a[1], t[1], st);
   } else {  // both masked or both not: one tile shape
     const dim3 grid(static_cast<unsigned>(nb0 + nb1));
-    if (t[0].wi == 2 && t[0].wj == 2) launch_wgrad_wide_pair<2, 2>(a[0], a[1], nb0, grid, st);
-    else if (t[0].wi == 2) launch_wgrad_wide_pair<2, 1>(a[0], a[1], nb0, grid, st);
-    else if (t[0].wj == 2) launch_wgrad_wide_pair<1, 2>(a[0], a[1], nb0, grid, st);
-    else if (a[0].gmask) hipLaunchKernelGGL((mlp_wgrad_pair_kernel<true>), grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
-    else hipLaunchKernelGGL((mlp_wgrad_pair_kernel<false>), grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
+    wgrad_dispatch(t[0], a[0].gmask != nullptr, [&](auto mask, auto wi, auto wj) {
+      hipLaunchKernelGGL((mlp_wgrad_pair_kernel<decltype(mask)::value, decltype(wi)::value, decltype(wj)::value>),
+                         grid, dim3(kWgThreads), 0, st, a[0], a[1], nb0);
+    });
   }
   TT_CHECK_LAUNCH();
   const int64_t len0 = static_cast<int64_t>(a[0].Ka + 1) * a[0].N, len1 = static_cast<int64_t>(a[1].Ka + 1) * a[1].N;

@@ -649,7 +649,8 @@ int tt_mlp_rows(const float* A, int64_t lda, const float* amask, int64_t ldam, c
  * (gmask != NULL: the layer's own ReluGrad).  dwb row-major with ld N — the
  * flat parameter layout of kernel [Ka, N] followed by bias [N].  bf16x3 MFMA,
  * batch split over workgroups, partials added in split order (deterministic;
- * workspace of tt_mlp_wgrad_workspace_size bytes).  Ka + 1 <= 288, N <= 256. */
+ * workspace of tt_mlp_wgrad_workspace_size bytes).  Ka in [1, 4096], N a
+ * multiple of 4 in [4, 4096]. */
 size_t tt_mlp_wgrad_workspace_size(int64_t M, int32_t Ka, int32_t N);
 int tt_mlp_wgrad(const float* A, int64_t lda, const float* G, int64_t ldg, const float* gmask, int64_t ldgm,
                  const float* scale, int64_t M, int32_t Ka, int32_t N, float* dwb, void* workspace,

@@ -1,9 +1,10 @@
-"""tt_mlp_wgrad's output tiles: the wide kernel (128 x 128 with
+"""tt_mlp_wgrad's output tiles: the wide forms (128 x 128 with
 TT_WGRAD_TILE=128; unset, 128 x 64 for masked problems and 64 x 128 otherwise)
-is bit-identical to the 64 x 64 reference kernel (TT_WGRAD_TILE=64, read at
-every call) through every entry (tt_mlp_wgrad, _pair, _adagrad), holds the
-project's fp32-faithful bound against torch fp64, and leaves the split counts
-alone.
+are bit-identical to the 64 x 64 form (TT_WGRAD_TILE=64, read at every call)
+through every entry (tt_mlp_wgrad, _pair, _adagrad), every form reproduces
+the recorded output digests of the stand-alone 64 x 64 kernel it replaced,
+holds the project's fp32-faithful bound against torch fp64, and leaves the
+split counts alone.
 
 The shapes are the smallest that reach each edge of the tiling: one row and
 one partial tile; a stage boundary with Ka + 1 = 64; Ka + 1 = 128 exactly; one
@@ -16,6 +17,7 @@ import functools
 import pytest
 import torch
 
+import wgrad_golden
 from pkg import _native
 from pkg.modelling import hip_ops
 
@@ -65,6 +67,25 @@ def test_wide_tile_bit_identical_to_64(cuda, monkeypatch, M, Ka, N, masked):
     assert torch.isfinite(ref).all()
     assert torch.equal(wide, ref)
     assert torch.equal(default, ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,Ka,N,masked", CASES)
+def test_every_tile_matches_recorded_64_digest(cuda, monkeypatch, M, Ka, N, masked):
+    """The anchor outside today's code: tests/golden/mlp_wgrad_tile64.json holds
+    the SHA-256 of what the stand-alone 64 x 64 kernel wrote for these inputs
+    at the last commit that had it (tests/golden/make_wgrad_golden.py); every
+    tile setting, "64" included, still writes exactly those bytes."""
+    a, g, gm, s = wgrad_golden.device_inputs(M, Ka, N, cuda)
+    want = wgrad_golden.recorded()["digests"][wgrad_golden.case_key(M, Ka, N, masked)]
+    for tile in wgrad_golden.TILES:
+        if tile is None:
+            monkeypatch.delenv("TT_WGRAD_TILE", raising=False)
+        else:
+            monkeypatch.setenv("TT_WGRAD_TILE", tile)
+        out = torch.full((Ka + 1, N), float("nan"), device=cuda)
+        hip_ops.mlp_wgrad(a, g, out, gmask=gm if masked else None, scale=s if masked else None)
+        assert wgrad_golden.digest(out) == want, f"TT_WGRAD_TILE={tile}"
 
 
 @pytest.mark.gpu
