@@ -90,6 +90,9 @@ __device__ __forceinline__ int a_off(int row, int ch) {
 // and -inf for padded rows; bias2 (if set) gets -inf on padded rows (its
 // [0, n) is written later by combine_rows).  One launch preps up to two
 // matrices (blockIdx.y); one block = 32 rows, 8 elements per thread.
+// ids (accidental-hit removal): the rows' int32 candidate ids, copied to
+// ids_dst [n_pad] (0 on padded rows: a padded streamed row's bias is -inf
+// already, a padded stationary row is discarded).
 struct PrepJob {
   const float* src;
   int64_t ld;
@@ -101,6 +104,8 @@ struct PrepJob {
   float* bias2;
   int vec;  // src 16-B aligned, ld % 4 == 0, dim % 4 == 0: float4 loads
   __bf16* dst_lo;  // x3 mode: also the residual plane bf16(x - bf16(x)) (NULL: none)
+  const int32_t* ids;  // hits mode: the rows' candidate ids (NULL: none)
+  int32_t* ids_dst;
 };
 
 template <int D>
@@ -148,6 +153,10 @@ __global__ void __launch_bounds__(256) prep_kernel(PrepJob j0, PrepJob j1, int d
     j.bias[r] = (r < j.n) ? (j.bv ? j.sign * j.bv[r] : 0.0f) : -INFINITY;
     if (j.bias2 && r >= j.n) j.bias2[r] = -INFINITY;
   }
+  if (j.ids_dst && threadIdx.x < 32) {
+    const int64_t r = r0 + threadIdx.x;
+    j.ids_dst[r] = r < j.n ? j.ids[r] : 0;
+  }
 }
 
 struct PassArgs {
@@ -163,6 +172,8 @@ struct PassArgs {
   float* part_o;          // [S, n_stat_pad, D]
   const __bf16* stat_lo;  // x3 mode: residual planes of the stationary / streamed rows
   const __bf16* strm_lo;
+  const int32_t* stat_ids;  // hits mode: [n_stat_pad] / [n_strm_pad] candidate ids
+  const int32_t* strm_ids;
 };
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -235,12 +246,27 @@ __device__ __forceinline__ void wait_vmcnt() {
 // hi + lo, both bf16; P split the same way in registers), three MFMAs where
 // the default issues one; the streamed rows' lo image has a ring of its own
 // (LDS 129 KB at D = 128: one workgroup per CU).
-template <int D, int MODE, bool X3 = false>
+//
+// HITS (opt-in, the tt_inbatch_*_hits entries): accidental-hit removal.  A
+// pair whose streamed row carries the stationary row's candidate id gets the
+// accumulator's initial value -inf where the others get the bias; -inf
+// survives the MFMA accumulation (finite products), so p = 0 in both passes
+// and the scores are not touched again: no work behind region A's MFMAs.
+// The tile's 64 streamed ids ride the ring in a slot beside its 64 biases
+// (one more dma_b32 of wave 0, read with the biases' ds_read_b128 pattern);
+// the wave's own 32 stationary ids sit in LDS and are read once per tile
+// (the X3 form has no register to keep one in).  The positive pair matches
+// by id as a rule but need not (the entries take any ids): mask_diag stays,
+// so it is excluded from the sums however the ids are filled.
+template <int D, int MODE, bool X3 = false, bool HITS = false>
 __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(const PassArgs a) {
   using G = Geo<D>;
   constexpr int IMG = X3 ? 2 : 1;                           // bf16 images per streamed tile
   constexpr int LO_OFF = kRingStages * G::A_BYTES;          // the lo ring (X3)
   constexpr int BIAS_OFF = IMG * kRingStages * G::A_BYTES;
+  constexpr int IDS_OFF = BIAS_OFF + kRingStages * kTile * 4;  // HITS: kRingStages x 64 streamed ids,
+  constexpr int SID_OFF = IDS_OFF + kRingStages * kTile * 4;   // then the workgroup's 128 stationary ids
+  constexpr int BDMA = HITS ? 2 : 1;                        // wave 0's 4-byte DMAs per tile
   extern __shared__ __attribute__((aligned(16))) char ring[];
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
   const int lane = lane_id();
@@ -270,6 +296,14 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
   const i32x4 desc = buffer_desc(a.strm, static_cast<unsigned>(a.n_strm_pad * D * 2));
   const i32x4 bdesc = buffer_desc(a.bias, static_cast<unsigned>(a.n_strm_pad * 4));
   const i32x4 ldesc = buffer_desc(X3 ? a.strm_lo : a.strm, static_cast<unsigned>(a.n_strm_pad * D * 2));
+  const i32x4 idesc = buffer_desc(HITS ? static_cast<const void*>(a.strm_ids) : a.bias,
+                                  static_cast<unsigned>(a.n_strm_pad * 4));
+  if constexpr (HITS) {
+    // a wave reads back only what its own lanes wrote (LDS ops of a wave
+    // complete in order): no barrier
+    if (h == 0)
+      *reinterpret_cast<volatile int*>(ring + SID_OFF + (wave * kRowsPerWave + l32) * 4) = a.stat_ids[stat_row];
+  }
   unsigned voff[G::PPW];
 #pragma unroll
   for (int u = 0; u < G::PPW; ++u) {
@@ -291,13 +325,16 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
       for (int u = 0; u < G::PPW; ++u)
         dma_b128(ldesc, voff[u], row0 * (D * 2), st + LO_OFF + (wave * G::PPW + u) * 1024);
     }
-    if (wave == 0) dma_b32(bdesc, lane * 4, row0 * 4, ring_lds + BIAS_OFF + stage * (kTile * 4));
+    if (wave == 0) {
+      dma_b32(bdesc, lane * 4, row0 * 4, ring_lds + BIAS_OFF + stage * (kTile * 4));
+      if constexpr (HITS) dma_b32(idesc, lane * 4, row0 * 4, ring_lds + IDS_OFF + stage * (kTile * 4));
+    }
   };
   // Wait until at most `ahead` issued tiles of this wave are still in flight.
   auto wait_tiles = [&](int ahead) {
     if (wave == 0) {
-      if (ahead >= 2) wait_vmcnt<2 * (IMG * G::PPW + 1)>();
-      else if (ahead == 1) wait_vmcnt<IMG * G::PPW + 1>();
+      if (ahead >= 2) wait_vmcnt<2 * (IMG * G::PPW + BDMA)>();
+      else if (ahead == 1) wait_vmcnt<IMG * G::PPW + BDMA>();
       else wait_vmcnt<0>();
     } else {
       if (ahead >= 2) wait_vmcnt<2 * IMG * G::PPW>();
@@ -358,13 +395,23 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
   };
   auto rd_bias = [&](int stage, f32x16* sacc) {
     const float* bias = reinterpret_cast<const float*>(ring + BIAS_OFF + stage * (kTile * 4)) + 4 * h;
+    int sid = 0;  // HITS: this lane's stationary id
+    if constexpr (HITS)
+      sid = *reinterpret_cast<const volatile int*>(ring + SID_OFF + (wave * kRowsPerWave + l32) * 4);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(bias + 32 * t + 8 * r4);
+        if constexpr (HITS) {
+          const i32x4 id4 = *reinterpret_cast<const i32x4*>(ring + IDS_OFF + stage * (kTile * 4) +
+                                                            (4 * h + 32 * t + 8 * r4) * 4);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) sacc[t][4 * r4 + u] = b4[u];
+          for (int u = 0; u < 4; ++u) sacc[t][4 * r4 + u] = id4[u] == sid ? -INFINITY : b4[u];
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sacc[t][4 * r4 + u] = b4[u];
+        }
       }
   };
 
@@ -872,9 +919,10 @@ struct PassWs {
   float* part_m;
   float* part_l;
   float* part_o;
+  int32_t *stat_ids, *strm_ids;  // hits mode only
 };
 
-PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false) {
+PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false) {
   PassWs w;
   w.stat = cv.take<__bf16>(p.stat_pad * p.D);
   w.strm = cv.take<__bf16>(p.strm_pad * p.D);
@@ -884,12 +932,15 @@ PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false) {
   w.part_m = cv.take<float>(int64_t(p.split) * p.stat_pad);
   w.part_l = cv.take<float>(int64_t(p.split) * p.stat_pad);
   w.part_o = cv.take<float>(int64_t(p.split) * p.stat_pad * p.D);
+  // after everything else: the plain entries' carve does not move
+  w.stat_ids = hits ? cv.take<int32_t>(p.stat_pad) : nullptr;
+  w.strm_ids = hits ? cv.take<int32_t>(p.strm_pad) : nullptr;
   return w;
 }
 
-size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false) {
+size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false, bool hits = false) {
   Carver cv(nullptr, 0);
-  carve_pass(cv, make_plan(n_stat, n_strm, dim), x3);
+  carve_pass(cv, make_plan(n_stat, n_strm, dim), x3, hits);
   return cv.used();
 }
 
@@ -953,35 +1004,45 @@ int combine_cols(int D, hipStream_t st, const float* po, int nsplit, int64_t n_s
   return TT_OK;
 }
 
-template <int D, int MODE, bool X3>
+template <int D, int MODE, bool X3, bool HITS>
 int launch_pass_d(dim3 grid, const PassArgs& a, hipStream_t st) {
-  constexpr int shm = Geo<D>::LDS_BYTES + (X3 ? kRingStages * Geo<D>::A_BYTES : 0);
+  // HITS: the streamed ids' ring slot and the workgroup's stationary ids
+  constexpr int shm = Geo<D>::LDS_BYTES + (X3 ? kRingStages * Geo<D>::A_BYTES : 0) +
+                      (HITS ? (kRingStages * kTile + kRowsPerWG) * 4 : 0);
   if (shm > 65536) {
-    static const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(inbatch_pass_kernel<D, MODE, X3>), hipFuncAttributeMaxDynamicSharedMemorySize, shm);
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(inbatch_pass_kernel<D, MODE, X3, HITS>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, shm);
     TT_CHECK_HIP(attr);
   }
   const int probe = MODE == 0 ? TT_PROBE_INBATCH_ROWS : TT_PROBE_INBATCH_COLS;
   const int reps = probe_reps(probe);  // > 1 only for a repeat probe (the pass is idempotent)
   probe_begin(probe, st);
   for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL((inbatch_pass_kernel<D, MODE, X3>), grid, dim3(kThreads), shm, st, a);
+    hipLaunchKernelGGL((inbatch_pass_kernel<D, MODE, X3, HITS>), grid, dim3(kThreads), shm, st, a);
   probe_end(MODE == 0 ? TT_PROBE_INBATCH_ROWS : TT_PROBE_INBATCH_COLS, st);
   TT_CHECK_LAUNCH();
   return TT_OK;
 }
 
-template <int MODE, bool X3 = false>
+template <int MODE, bool X3 = false, bool HITS = false>
 int launch_pass(const Plan& p, const PassArgs& a, hipStream_t st) {
   // buffer descriptors address the bf16 images with 32-bit byte offsets
   if (p.strm_pad * p.D * 2 >= (1ll << 31))
     return fail(TT_ERR_UNSUPPORTED, "inbatch: %lld x %d streamed batch too large", (long long)p.strm_pad, p.D);
   dim3 grid(static_cast<unsigned>(p.stat_pad / kRowsPerWG), static_cast<unsigned>(p.split));
   switch (p.D) {
-    case 32: return launch_pass_d<32, MODE, X3>(grid, a, st);
-    case 64: return launch_pass_d<64, MODE, X3>(grid, a, st);
-    default: return launch_pass_d<128, MODE, X3>(grid, a, st);
+    case 32: return launch_pass_d<32, MODE, X3, HITS>(grid, a, st);
+    case 64: return launch_pass_d<64, MODE, X3, HITS>(grid, a, st);
+    default: return launch_pass_d<128, MODE, X3, HITS>(grid, a, st);
   }
+}
+
+// a.stat_ids != NULL: the accidental-hit form of the pass
+template <int MODE>
+int launch_pass_any(const Plan& p, const PassArgs& a, bool x3, hipStream_t st) {
+  if (a.stat_ids) return x3 ? launch_pass<MODE, true, true>(p, a, st) : launch_pass<MODE, false, true>(p, a, st);
+  return x3 ? launch_pass<MODE, true>(p, a, st) : launch_pass<MODE>(p, a, st);
 }
 
 int check_common(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc, int64_t n_cols,
@@ -1002,18 +1063,20 @@ using namespace tt;
 
 namespace tt {
 namespace {
-size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3) {
+size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, bool hits = false) {
   if (n_rows < 1 || n_cols < 1 || pick_dpad(dim) == 0) return 0;
-  const size_t a = pass_bytes(n_rows, n_cols, dim, x3);
-  const size_t b = pass_bytes(n_cols, n_rows, dim, x3);
+  const size_t a = pass_bytes(n_rows, n_cols, dim, x3, hits);
+  const size_t b = pass_bytes(n_cols, n_rows, dim, x3, hits);
   return a > b ? a : b;
 }
 
 // The rows / cols entries' bodies; x3: the bf16x3 form (residual planes of
 // both operands beside the bf16 images, inbatch_pass_kernel<D, MODE, true>).
-int xent_rows(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
-              int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset, float* lse, float* row_loss,
-              float* dq, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+// row_ids / col_ids (both or neither): the accidental-hit form (HITS).
+int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
+              int64_t n_rows, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
+              int64_t pos_offset, float* lse, float* row_loss, float* dq, void* workspace, size_t workspace_bytes,
+              tt_stream_t stream) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && row_loss, "%s: NULL lse/row_loss", fn);
@@ -1021,7 +1084,7 @@ int xent_rows(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_ro
              "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
   const Plan p = make_plan(n_rows, n_cols, dim);
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3);
+  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
@@ -1029,18 +1092,21 @@ int xent_rows(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_ro
   PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
   jq.dst_lo = w.stat_lo;
   jc.dst_lo = w.strm_lo;
+  jq.ids = row_ids, jq.ids_dst = w.stat_ids;
+  jc.ids = col_ids, jc.ids_dst = w.strm_ids;
   if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
   if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, w.part_m, w.part_l, w.part_o,
-             w.stat_lo, w.strm_lo};
-  if ((rc = x3 ? launch_pass<0, true>(p, a, st) : launch_pass<0>(p, a, st))) return rc;
+             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids};
+  if ((rc = launch_pass_any<0>(p, a, x3, st))) return rc;
   return combine_rows(p.D, st, w.part_m, w.part_l, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, logq, n_rows, dim,
                       pos_offset, lse, row_loss, dq, nullptr);
 }
 
-int xent_cols(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_rows, const float* lse,
-              const float* row_loss, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
-              int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
+              int64_t n_rows, const float* lse, const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
+              int32_t dim, const float* logq, int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes,
+              tt_stream_t stream) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && dc, "%s: NULL lse/dc", fn);
@@ -1048,7 +1114,7 @@ int xent_cols(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_ro
              "%s: positives [pos_offset, pos_offset+n_cols) exceed n_rows", fn);
   const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3);
+  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
@@ -1056,11 +1122,13 @@ int xent_cols(const char* fn, bool x3, const float* q, int64_t ldq, int64_t n_ro
   PrepJob jc = prep_job(c, ldc, n_cols, dim, w.stat), jq = prep_job(q, ldq, n_rows, dim, w.strm, lse, w.bias);
   jc.dst_lo = w.stat_lo;
   jq.dst_lo = w.strm_lo;
+  jc.ids = col_ids, jc.ids_dst = w.stat_ids;
+  jq.ids = row_ids, jq.ids_dst = w.strm_ids;
   if ((rc = prep(p.D, jc, none, dim, p.stat_pad, st))) return rc;
   if ((rc = prep(p.D, jq, none, dim, p.strm_pad, st))) return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o,
-             w.stat_lo, w.strm_lo};
-  if ((rc = x3 ? launch_pass<1, true>(p, a, st) : launch_pass<1>(p, a, st))) return rc;
+             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids};
+  if ((rc = launch_pass_any<1>(p, a, x3, st))) return rc;
   return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
                       pos_offset, dc);
 }
@@ -1076,8 +1144,8 @@ extern "C" int tt_inbatch_xent_rows(const float* q, int64_t ldq, int64_t n_rows,
                                     float* lse, float* row_loss, float* dq, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_rows("tt_inbatch_xent_rows", false, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset, lse,
-                   row_loss, dq, workspace, workspace_bytes, stream);
+  return xent_rows("tt_inbatch_xent_rows", false, nullptr, nullptr, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
+                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1085,8 +1153,8 @@ extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows,
                                     const float* logq, int64_t pos_offset, float* dc, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_cols("tt_inbatch_xent_cols", false, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
-                   pos_offset, dc, workspace, workspace_bytes, stream);
+  return xent_cols("tt_inbatch_xent_cols", false, nullptr, nullptr, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols,
+                   dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // The same two entries with fp32-faithful products (X3, as
@@ -1102,8 +1170,8 @@ extern "C" int tt_inbatch_xent_rows_x3(const float* q, int64_t ldq, int64_t n_ro
                                        float* lse, float* row_loss, float* dq, void* workspace,
                                        size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_rows("tt_inbatch_xent_rows_x3", true, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset, lse,
-                   row_loss, dq, workspace, workspace_bytes, stream);
+  return xent_rows("tt_inbatch_xent_rows_x3", true, nullptr, nullptr, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
+                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols_x3(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1111,8 +1179,36 @@ extern "C" int tt_inbatch_xent_cols_x3(const float* q, int64_t ldq, int64_t n_ro
                                        int32_t dim, const float* logq, int64_t pos_offset, float* dc,
                                        void* workspace, size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_cols("tt_inbatch_xent_cols_x3", true, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
-                   pos_offset, dc, workspace, workspace_bytes, stream);
+  return xent_cols("tt_inbatch_xent_cols_x3", true, nullptr, nullptr, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols,
+                   dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
+}
+
+// Accidental-hit removal (HITS): the same entries over S' with the pairs
+// (i, j != pos(i)) of equal candidate id at -inf; x3 != 0: the bf16x3 form.
+extern "C" size_t tt_inbatch_hits_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim, int32_t x3) {
+  return inbatch_ws_size(n_rows, n_cols, dim, x3 != 0, true);
+}
+
+extern "C" int tt_inbatch_xent_rows_hits(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
+                                         int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset,
+                                         const int32_t* row_ids, const int32_t* col_ids, int32_t x3, float* lse,
+                                         float* row_loss, float* dq, void* workspace, size_t workspace_bytes,
+                                         tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(row_ids && col_ids, "tt_inbatch_xent_rows_hits: NULL row_ids/col_ids");
+  return xent_rows("tt_inbatch_xent_rows_hits", x3 != 0, row_ids, col_ids, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
+                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tt_inbatch_xent_cols_hits(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+                                         const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
+                                         int32_t dim, const float* logq, int64_t pos_offset, const int32_t* row_ids,
+                                         const int32_t* col_ids, int32_t x3, float* dc, void* workspace,
+                                         size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(row_ids && col_ids, "tt_inbatch_xent_cols_hits: NULL row_ids/col_ids");
+  return xent_cols("tt_inbatch_xent_cols_hits", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
+                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1126,6 +1222,7 @@ struct FusedWs {
   __bf16 *qb_lo, *cb_lo;  // x3 mode only
   float *bias_logq, *bias_lse;
   float *part_m, *part_l, *part_o_rows, *part_o_cols;
+  int32_t* ids;  // hits mode only: [n_pad], both passes' stationary and streamed ids
 };
 struct FusedPlan {
   int D;
@@ -1141,7 +1238,7 @@ FusedPlan fused_plan(int64_t n, int dim) {
   p.per_split = round_up(ceil_div(p.n_pad, p.split), kTile);
   return p;
 }
-FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false) {
+FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false, bool hits = false) {
   FusedWs w;
   w.qb = cv.take<__bf16>(p.n_pad * p.D);
   w.cb = cv.take<__bf16>(p.n_pad * p.D);
@@ -1153,6 +1250,7 @@ FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false) {
   w.part_l = cv.take<float>(int64_t(p.split) * p.n_pad);
   w.part_o_rows = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
   w.part_o_cols = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
+  w.ids = hits ? cv.take<int32_t>(p.n_pad) : nullptr;  // last: the plain carve does not move
   return w;
 }
 }  // namespace
@@ -1172,13 +1270,14 @@ namespace {
 // workspace, ordered before this call).
 int softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n, int32_t dim, const float* logq,
                  float* lse, float* row_loss, float* dq, float* dc, void* workspace, size_t workspace_bytes,
-                 tt_stream_t stream, bool prepped, float loss_scale = 1.0f, float* loss = nullptr, bool x3 = false) {
+                 tt_stream_t stream, bool prepped, float loss_scale = 1.0f, float* loss = nullptr, bool x3 = false,
+                 const int32_t* ids = nullptr) {
   int rc = check_common(q, ldq, n, c, ldc, n, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && row_loss && dq && dc, "tt_inbatch_softmax_xent: NULL output");
   const FusedPlan p = fused_plan(n, dim);
   Carver cv(workspace, workspace_bytes);
-  FusedWs w = carve_fused(cv, p, x3);
+  FusedWs w = carve_fused(cv, p, x3, ids != nullptr);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "tt_inbatch_softmax_xent: workspace %zu < required %zu", workspace_bytes,
                 cv.used());
@@ -1187,17 +1286,18 @@ int softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64
   PrepJob jq = prep_job(q, ldq, n, dim, w.qb), jc = prep_job(c, ldc, n, dim, w.cb, logq, w.bias_logq, w.bias_lse);
   jq.dst_lo = w.qb_lo;
   jc.dst_lo = w.cb_lo;
+  jc.ids = ids, jc.ids_dst = w.ids;  // one padded copy serves rows and columns
   if (!prepped && (rc = prep(p.D, jq, jc, dim, p.n_pad, st))) return rc;
   const Plan pl{p.D, p.n_pad, p.n_pad, p.split, p.per_split};
   PassArgs ar{w.qb, w.cb, w.bias_logq, p.n_pad, p.n_pad, p.per_split, 0, w.part_m, w.part_l, w.part_o_rows,
-              w.qb_lo, w.cb_lo};
-  if ((rc = x3 ? launch_pass<0, true>(pl, ar, st) : launch_pass<0>(pl, ar, st))) return rc;
+              w.qb_lo, w.cb_lo, w.ids, w.ids};
+  if ((rc = launch_pass_any<0>(pl, ar, x3, st))) return rc;
   if ((rc = combine_rows(p.D, st, w.part_m, w.part_l, w.part_o_rows, p.split, p.n_pad, q, ldq, c, ldc, logq, n, dim,
                          0, lse, row_loss, dq, w.bias_lse)))
     return rc;
   PassArgs ac{w.cb, w.qb, w.bias_lse, p.n_pad, p.n_pad, p.per_split, 0, nullptr, nullptr, w.part_o_cols,
-              w.cb_lo, w.qb_lo};
-  if ((rc = x3 ? launch_pass<1, true>(pl, ac, st) : launch_pass<1>(pl, ac, st))) return rc;
+              w.cb_lo, w.qb_lo, w.ids, w.ids};
+  if ((rc = launch_pass_any<1>(pl, ac, x3, st))) return rc;
   return combine_cols(p.D, st, w.part_o_cols, p.split, p.n_pad, q, ldq, c, ldc, lse, row_loss, logq, n, dim, 0, dc,
                       loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
 }
@@ -1271,4 +1371,25 @@ extern "C" int tt_inbatch_softmax_xent_x3(const float* q, int64_t ldq, const flo
   clear_error();
   return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
                       loss_scale, loss, true);
+}
+
+// Accidental-hit removal (HITS), single device: ids [n] are both the rows'
+// and the columns' candidate ids; loss may be NULL; x3 != 0: the bf16x3 form.
+extern "C" size_t tt_inbatch_fused_hits_workspace_size(int64_t n, int32_t dim, int32_t x3) {
+  if (n < 1 || pick_dpad(dim) == 0) return 0;
+  Carver cv(nullptr, 0);
+  carve_fused(cv, fused_plan(n, dim), x3 != 0, true);
+  return cv.used();
+}
+
+extern "C" int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
+                                            int32_t dim, const float* logq, const int32_t* ids, int32_t x3,
+                                            float* lse, float* row_loss, float* dq, float* dc, float loss_scale,
+                                            float* loss, void* workspace, size_t workspace_bytes,
+                                            tt_stream_t stream) {
+  using namespace tt;
+  clear_error();
+  TT_REQUIRE(ids, "tt_inbatch_softmax_xent_hits: NULL ids");
+  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
+                      loss_scale, loss, x3 != 0, ids);
 }

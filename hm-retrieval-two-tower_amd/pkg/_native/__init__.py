@@ -291,6 +291,23 @@ _PROTOS = {
         [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
          c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "tt_inbatch_hits_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "tt_inbatch_xent_rows_hits": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_xent_cols_hits": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_fused_hits_workspace_size": (c_size_t, [c_int64, c_int32, c_int32]),
+    "tt_inbatch_softmax_xent_hits": (
+        c_int32,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "tt_bruteforce_index_bytes": (c_size_t, [c_int64, c_int32]),
     "tt_bruteforce_build": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "tt_bruteforce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),

@@ -829,6 +829,9 @@ class ShardedTrainStep:
     the eager one); over gloo it runs eagerly.
     global_negatives=False keeps per-replica negatives (a labelled variant:
     each rank's loss over its own batch).
+    A model with remove_accidental_hits hands the loss this rank's candidate
+    ids either way (global negatives: one more all_gather of [b] int32 per
+    step, captured with the others).
 
     Adagrad (the reference's optimizer, main.py:100-101) only.
     """
@@ -1022,9 +1025,9 @@ class ShardedTrainStep:
             if m.loss.reduction != "sum":
                 raise NotImplementedError("global negatives: the reference's SUM reduction only")
             loss = global_towers_inbatch_softmax_xent(qi, ci, m.query_tower.dense, m.candidate_tower.dense,
-                                                      self.comm, m.candidate_logq(x))
+                                                      self.comm, m.candidate_logq(x), m.candidate_ids(x))
         else:
-            loss = m.tower_loss(qi, ci, m.candidate_logq(x))
+            loss = m.tower_loss(qi, ci, m.candidate_logq(x), m.candidate_ids(x))
         for t in m.towers:
             t.dense.flat.grad = None
         if getattr(self, "_one", None) is None:

@@ -123,7 +123,8 @@ def save_two_tower(model, path_noext: str) -> None:
             "candidate_id_col": model.candidate_id_col,
             "joint_embedding_size": model.query_tower.joint_embedding_size,
             "query_tower_units": model.query_tower.hidden_units,
-            "candidate_tower_units": model.candidate_tower.hidden_units}
+            "candidate_tower_units": model.candidate_tower.hidden_units,
+            "remove_accidental_hits": bool(model.remove_accidental_hits)}
     arrays = _vocab_arrays(model.query_features, "query.")
     arrays.update(_vocab_arrays(model.candidate_features, "candidate."))
     arrays["logq.keys"] = np.asarray(list(lookup.keys()), dtype=str)
@@ -142,7 +143,8 @@ def load_two_tower(path_noext: str, device=None):
     model = TwoTowerModel(_features_from(meta["query_features"], arrays, "query."),
                           _features_from(meta["candidate_features"], arrays, "candidate."),
                           meta["candidate_id_col"], meta["joint_embedding_size"], meta["query_tower_units"],
-                          meta["candidate_tower_units"], candidate_prob_lookup=lookup, device=_device(device))
+                          meta["candidate_tower_units"], candidate_prob_lookup=lookup, device=_device(device),
+                          remove_accidental_hits=bool(meta.get("remove_accidental_hits", False)))
     model.query_tower.load_state_dict({k[len("query_tower."):]: v for k, v in tensors.items()
                                        if k.startswith("query_tower.")})
     model.candidate_tower.load_state_dict({k[len("candidate_tower."):]: v for k, v in tensors.items()

@@ -793,10 +793,42 @@ def _opt_ptr(t: Optional[torch.Tensor], name: str, n: int) -> Optional[int]:
     return t.data_ptr()
 
 
+def _ids_ptr(t: torch.Tensor, name: str, like: torch.Tensor) -> int:
+    """Candidate ids of the accidental-hit entries: a contiguous int32 vector,
+    one id per row of `like`, on its device (checked before the operands, so
+    a bad id vector is reported as such wherever the operands live)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name} must be torch.int32, got {t.dtype}")
+    n = like.shape[0]
+    if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [{n}] int32 tensor, got shape {tuple(t.shape)}")
+    if t.device != like.device:
+        raise ValueError(f"{name} must live on the operands' device {like.device} (got {t.device})")
+    return t.data_ptr()
+
+
+def _ids_pair(row_ids, col_ids, rows: torch.Tensor, cols: torch.Tensor):
+    """(row_ids pointer, col_ids pointer), or None when neither is given."""
+    if (row_ids is None) != (col_ids is None):
+        raise ValueError("row_ids and col_ids go together (both or neither)")
+    if row_ids is None:
+        return None
+    return _ids_ptr(row_ids, "row_ids", rows), _ids_ptr(col_ids, "col_ids", cols)
+
+
 def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], pos_offset: int = 0,
-                 want_dq: bool = True, x3: bool = False):
+                 want_dq: bool = True, x3: bool = False, row_ids: Optional[torch.Tensor] = None,
+                 col_ids: Optional[torch.Tensor] = None):
     """Row pass: (lse [R], row_loss [R], dq [R,E] or None).  x3: fp32-faithful
-    products (tt_inbatch_xent_rows_x3, as inbatch_fused(x3=True))."""
+    products (tt_inbatch_xent_rows_x3, as inbatch_fused(x3=True)).
+    row_ids [R], col_ids [C] (int32, both or neither): accidental hits
+    removed (tt_inbatch_xent_rows_hits) — a column j other than row i's
+    positive with col_ids[j] == row_ids[i] is no negative of row i.  Ids are
+    compared for equality only, so all out-of-vocabulary rows (id 0) count
+    as one candidate."""
+    hits = _ids_pair(row_ids, col_ids, q, c)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
     ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
@@ -805,36 +837,58 @@ def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
     if c.shape[1] != E:
         raise ValueError("q and c must share the embedding size")
     L = lib()
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3)
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
     lse = torch.empty(R, dtype=torch.float32, device=q.device)
     row_loss = torch.empty(R, dtype=torch.float32, device=q.device)
     dq = torch.empty(R, E, dtype=torch.float32, device=q.device) if want_dq else None
+    if hits is not None:
+        rid, cid = hits
+        check(L.tt_inbatch_xent_rows_hits(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
+                                          pos_offset, rid, cid, int(x3), lse.data_ptr(), row_loss.data_ptr(),
+                                          dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(),
+                                          _stream()))
+        return lse, row_loss, dq
     fn = L.tt_inbatch_xent_rows_x3 if x3 else L.tt_inbatch_xent_rows
     check(fn(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C), pos_offset, lse.data_ptr(),
              row_loss.data_ptr(), dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(), _stream()))
     return lse, row_loss, dq
 
 
-def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool) -> torch.Tensor:
-    """The rows / cols entries' workspace (x3: the larger one of its own)."""
+def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool,
+                       hits: bool = False) -> torch.Tensor:
+    """The rows / cols entries' workspace (x3, hits: larger ones of their own)."""
+    if hits:
+        return Workspace.get(L.tt_inbatch_hits_workspace_size(R, C, E, int(x3)), device,
+                             "inbatch_hits_x3" if x3 else "inbatch_hits")
     if x3:
         return Workspace.get(L.tt_inbatch_x3_workspace_size(R, C, E), device, "inbatch_x3")
     return Workspace.get(L.tt_inbatch_workspace_size(R, C, E), device, "inbatch")
 
 
 def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
-                 pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None, x3: bool = False) -> torch.Tensor:
+                 pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None, x3: bool = False,
+                 row_ids: Optional[torch.Tensor] = None, col_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Column pass: dc [C,E] from every row's q [R,E], lse [R] and (optional,
     for the exact 1 - P_pos of confident rows) row_loss [R].  x3: fp32-faithful
-    products (tt_inbatch_xent_cols_x3)."""
+    products (tt_inbatch_xent_cols_x3).  row_ids [R], col_ids [C] (int32, both
+    or neither): accidental hits removed as in inbatch_rows, whose lse and
+    row_loss must come from the same ids (tt_inbatch_xent_cols_hits)."""
+    hits = _ids_pair(row_ids, col_ids, q, c)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
     ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
     R, E = q.shape
     C = c.shape[0]
     L = lib()
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3)
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
     dc = torch.empty(C, E, dtype=torch.float32, device=q.device)
+    if hits is not None:
+        rid, cid = hits
+        check(L.tt_inbatch_xent_cols_hits(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
+                                          _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
+                                          _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3), dc.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()))
+        return dc
     fn = L.tt_inbatch_xent_cols_x3 if x3 else L.tt_inbatch_xent_cols
     check(fn(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
              _opt_ptr(logq, "logq", C), pos_offset, dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
@@ -859,14 +913,23 @@ def inbatch_prep(x: torch.Tensor, operand: int, logq: Optional[torch.Tensor], ws
 
 
 def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], ws: Optional[torch.Tensor] = None,
-                  prepped: bool = False, loss_scale: Optional[float] = None, x3: bool = False):
+                  prepped: bool = False, loss_scale: Optional[float] = None, x3: bool = False,
+                  ids: Optional[torch.Tensor] = None):
     """Single-device loss + gradients (both passes, shared bf16 prep):
     (lse [B], row_loss [B], dq [B,E], dc [B,E]).  prepped: both operands were
     already prepared into `ws` by inbatch_prep (ordered before this call).
     loss_scale: also return the loss loss_scale * sum(row_loss) (a 0-d
     tensor, computed inside the last launch, equal to loss_sum's).
     x3: fp32-faithful products (tt_inbatch_softmax_xent_x3: S and P.V as
-    bf16x3 products, ~3x the passes' time; not with prepped)."""
+    bf16x3 products, ~3x the passes' time; not with prepped).
+    ids [B] (int32): accidental hits removed (tt_inbatch_softmax_xent_hits) —
+    a column j != i with ids[j] == ids[i] is no negative of row i; equality
+    only, so all out-of-vocabulary rows (id 0) count as one candidate.  This
+    departs from the reference's loss; not with prepped."""
+    if ids is not None:
+        if prepped:
+            raise ValueError("ids: the accidental-hit entry prepares its operands itself (prepped=False)")
+        idp = _ids_ptr(ids, "ids", q)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
     ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
@@ -876,6 +939,20 @@ def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor]
     if prepped and ws is None:
         raise ValueError("prepped=True needs the workspace the operands were prepared into")
     L = lib()
+    if ids is not None:
+        ws = Workspace.get(L.tt_inbatch_fused_hits_workspace_size(B, E, int(x3)), q.device,
+                           "inbatch_fused_hits_x3" if x3 else "inbatch_fused_hits")
+        lse = torch.empty(B, dtype=torch.float32, device=q.device)
+        row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
+        dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
+        dc = torch.empty(B, E, dtype=torch.float32, device=q.device)
+        loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
+        check(L.tt_inbatch_softmax_xent_hits(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
+                                             idp, int(x3), lse.data_ptr(), row_loss.data_ptr(), dq.data_ptr(),
+                                             dc.data_ptr(), float(loss_scale if loss_scale is not None else 1.0),
+                                             loss.data_ptr() if loss is not None else None, ws.data_ptr(),
+                                             ws.numel(), _stream()))
+        return (lse, row_loss, dq, dc, loss) if loss is not None else (lse, row_loss, dq, dc)
     if x3:
         if prepped:
             raise ValueError("x3: the fp32-faithful entry prepares its operands itself (prepped=False)")

@@ -40,10 +40,19 @@ def x3_scores() -> bool:
     return os.environ.get("TT_INBATCH_X3", "0") == "1"
 
 
+# ids (every loss below, optional): the int32 candidate id of each row's
+# positive.  Given, accidental hits are removed: a column j other than row i's
+# own with ids[j] == ids[i] (the same article again in the batch) is no
+# negative of row i, in the loss and in both gradients (include/tt.h,
+# tt_inbatch_*_hits; TensorFlow Recommenders' remove_accidental_hits).  Ids
+# are compared for equality only, so all out-of-vocabulary rows (id 0) count
+# as one candidate.  The reference has no such option: ids=None is its loss.
+
+
 class _InBatchXent(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, c, logq, scale):
-        lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores())
+    def forward(ctx, q, c, logq, scale, ids=None):
+        lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids)
         ctx.scale = scale
         ctx.save_for_backward(dq, dc)
         return hip_ops.loss_sum(row_loss, scale)
@@ -52,7 +61,7 @@ class _InBatchXent(torch.autograd.Function):
     def backward(ctx, g):
         dq, dc = ctx.saved_tensors
         s = g * ctx.scale
-        return dq * s, dc * s, None, None
+        return dq * s, dc * s, None, None, None
 
 
 _SIDE: dict = {}
@@ -155,18 +164,19 @@ class _TowersInBatchXent(torch.autograd.Function):
     a device scalar (no separate scaling pass over dQ, dC)."""
 
     @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None):
+    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None):
         ctx.pair = _paired(qi, stack_q, stack_c)
         ctx.on_dx = on_dx
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
-            return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower)
+            return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower,
+                                              ids=ids)
         main = torch.cuda.current_stream()
         side = _tower_stream(qi.device)
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
-        # (not under x3_scores(): that entry prepares its operands itself)
-        split_prep = SPLIT_PREP and not x3_scores()
+        # (not under x3_scores() or with ids: those entries prepare their operands themselves)
+        split_prep = SPLIT_PREP and not x3_scores() and ids is None
         ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
         with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
@@ -177,14 +187,20 @@ class _TowersInBatchXent(torch.autograd.Function):
         if ws is not None:
             hip_ops.inbatch_prep(qa[-1], 0, None, ws)
         main.wait_stream(side)
-        return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws)
+        return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws,
+                                          ids)
 
     @staticmethod
-    def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None):
+    def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None, ids=None):
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
         ctx.scale = scale
         ctx.on_tower = on_tower
+        if ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
+            _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, loss_scale=scale, x3=x3_scores(),
+                                                       ids=ids)
+            ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
+            return loss
         if x3_scores():  # fp32-faithful scores (its own preparation and workspace)
             _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, loss_scale=scale, x3=True)
             ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
@@ -204,7 +220,7 @@ class _TowersInBatchXent(torch.autograd.Function):
         stack_q, stack_c = ctx.stacks
         if ctx.pair:  # (on_dx unused: on_tower then applies each tower's whole update)
             return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, ctx.on_tower),
-                    None, None, None, None, None, None)
+                    None, None, None, None, None, None, None)
         on_dx = ctx.on_dx
         main = torch.cuda.current_stream()
         side = _tower_stream(dq.device)
@@ -221,11 +237,11 @@ class _TowersInBatchXent(torch.autograd.Function):
         if ctx.on_tower is not None:
             ctx.on_tower(0, gqi, gflat_q)
         main.wait_stream(side)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None
 
 
 def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], comm,
-                         rows=None, cols=None, x3: Optional[bool] = None):
+                         rows=None, cols=None, x3: Optional[bool] = None, ids: Optional[torch.Tensor] = None):
     """This rank's share of the in-batch loss over the GLOBAL batch
     (two_tower_model.py:113-122 with the batch split over the ranks: row i's
     negatives are every candidate of every rank).  q, c: this rank's [b, E]
@@ -237,13 +253,17 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     the local candidates, so every gradient is summed inside one kernel in a
     fixed order (no cross-rank reduction of partial sums).  x3: fp32-faithful
     products in the library's entries (None: x3_scores(), the flag read at
-    this call); injected rows / cols are called as they are."""
+    this call); injected rows / cols are called as they are.  ids: this
+    rank's [b] int32 candidate ids — accidental hits removed over the global
+    batch: the ids are all-gathered once, and the gathered vector is the rows
+    pass's col_ids and the cols pass's row_ids (injected rows / cols receive
+    row_ids / col_ids as keywords)."""
     if x3 is None:
         x3 = x3_scores()
     if WORLD1_FUSED and comm.world == 1 and rows is None and cols is None and not getattr(comm, "always", False):
         # one rank: its rows are every row and its columns every column — the
         # single-device entry (one shared preparation of q and c for both passes)
-        _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3)
+        _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids)
         return row_loss, dq, dc
     rows = rows or (functools.partial(hip_ops.inbatch_rows, x3=True) if x3 else hip_ops.inbatch_rows)
     cols = cols or (functools.partial(hip_ops.inbatch_cols, x3=True) if x3 else hip_ops.inbatch_cols)
@@ -251,6 +271,10 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     off = comm.rank * b
     C = comm.all_gather(c)                                     # [G b, E]
     L = comm.all_gather(logq) if logq is not None else None   # [G b]
+    if ids is not None:
+        I = comm.all_gather(ids)                               # [G b]: every candidate's id
+        rows = functools.partial(rows, row_ids=ids, col_ids=I)
+        cols = functools.partial(cols, row_ids=I, col_ids=ids)
     lse, row_loss, dq = rows(q, C, L, pos_offset=off)
     Qa = comm.all_gather(q)                                    # [G b, E]
     if comm.world == 1 and not getattr(comm, "always", False):
@@ -268,7 +292,7 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
     gradients) over the ranks."""
 
     @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm):
+    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm, ids=None):
         ctx.pair = _paired(qi, stack_q, stack_c)
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
@@ -278,7 +302,7 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
                 ca = stack_c.forward_acts(ci, flat_c)
             qa = stack_q.forward_acts(qi, flat_q)
             _tower_join(qi)
-        row_loss, dq, dc = global_inbatch_grads(qa[-1], ca[-1], logq, comm)
+        row_loss, dq, dc = global_inbatch_grads(qa[-1], ca[-1], logq, comm, ids=ids)
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
         ctx.scale = scale
@@ -292,49 +316,52 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
         s = (g * ctx.scale if ctx.scale != 1.0 else g).reshape(1).float().contiguous()
         stack_q, stack_c = ctx.stacks
         if ctx.pair:
-            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None)
+            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None, None)
         with _TowerFork(dq):
             gci, gflat_c = stack_c.backward_acts(ca, flat_c, dc, s, ctx.needs_input_grad[1])
         gqi, gflat_q = stack_q.backward_acts(qa, flat_q, dq, s, ctx.needs_input_grad[0])
         _tower_join(dq)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None
 
 
 def global_towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c, comm,
-                                       logq: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                       logq: Optional[torch.Tensor] = None,
+                                       ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """towers_inbatch_softmax_xent with the negatives of every rank (SUM
-    reduction, the reference's runner.py:78-83)."""
-    return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm)
+    reduction, the reference's runner.py:78-83).  ids: this rank's candidate
+    ids (accidental hits removed over the global batch)."""
+    return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm, ids)
 
 
 def towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c,
                                 logq: Optional[torch.Tensor] = None, reduction: str = "sum",
-                                on_tower=None, on_dx=None) -> torch.Tensor:
+                                on_tower=None, on_dx=None, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Loss of the query tower on qi against the candidate tower on ci (tower
     inputs [B, *]), fused into one autograd node; stack_* are DenseStacks.
     on_tower(i, input_grad, flat_grad), if given, is called in the backward as
     soon as tower i's (0 query, 1 candidate) gradients exist, on the stream and
     workspace scope they were produced in (the fused train step applies the
-    optimizer there)."""
+    optimizer there).  ids [B] (int32): accidental hits removed."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / qi.shape[0]
     return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, on_tower,
-                                    on_dx)
+                                    on_dx, ids)
 
 
 def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor] = None,
-                         reduction: str = "sum") -> torch.Tensor:
+                         reduction: str = "sum", ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Loss of query rows q [B,E] against candidates c [B,E] (positive of row
-    i is column i), logq [B] the per-candidate log sampling probability."""
+    i is column i), logq [B] the per-candidate log sampling probability.
+    ids [B] (int32): accidental hits removed (see above)."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / q.shape[0]
     if not q.requires_grad and not c.requires_grad:
         # the scores the training loss is computed from, in either mode
-        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores())
+        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids, col_ids=ids)
         return hip_ops.loss_sum(row_loss, scale)
-    return _InBatchXent.apply(q, c, logq, scale)
+    return _InBatchXent.apply(q, c, logq, scale, ids)
 
 
 class InBatchSoftmaxCrossEntropy:
@@ -346,8 +373,8 @@ class InBatchSoftmaxCrossEntropy:
             raise ValueError("the in-batch loss is defined on logits (from_logits=True)")
         self.reduction = str(reduction).lower().split(".")[-1]
 
-    def __call__(self, q, c, logq=None):
-        return inbatch_softmax_xent(q, c, logq, self.reduction)
+    def __call__(self, q, c, logq=None, ids=None):
+        return inbatch_softmax_xent(q, c, logq, self.reduction, ids)
 
 
 # Name the reference compiles with.

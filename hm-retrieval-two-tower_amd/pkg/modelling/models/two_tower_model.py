@@ -72,6 +72,13 @@ class TwoTowerModel(AbstractKerasModel):
         Hidden units for the candidate tower.
     candidate_prob_lookup: Optional[Dict[str, float]]
         If provided, logQ correction is applied before the loss.
+    remove_accidental_hits: bool
+        Off (the default): the reference's loss, every other column of the
+        batch a negative.  On: a column that holds the same candidate as a
+        row's own positive (equal encoded candidate_id_col; all
+        out-of-vocabulary candidates, id 0, count as one) is no negative of
+        that row, in training and in evaluation — a departure from the
+        reference's loss (TensorFlow Recommenders' remove_accidental_hits).
     """
 
     def __init__(self, query_features: List[Feature], candidate_features: List[Feature], candidate_id_col: str,
@@ -79,7 +86,8 @@ class TwoTowerModel(AbstractKerasModel):
                  candidate_tower_units: Optional[List[int]] = None,
                  candidate_prob_lookup: Optional[Dict[str, float]] = None,
                  device: Optional[torch.device] = None, seed: Optional[int] = None,
-                 fused_optimizer_apply: bool = False):
+                 fused_optimizer_apply: bool = False, remove_accidental_hits: bool = False):
+        self.remove_accidental_hits = bool(remove_accidental_hits)
         # apply each tower's Adagrad step inside the backward (see train_step)
         self.fused_optimizer_apply = bool(fused_optimizer_apply)
         self.query_features = query_features
@@ -144,6 +152,17 @@ class TwoTowerModel(AbstractKerasModel):
         hip_ops.gather_grouped([(self._logq_rows.view(-1, 1), ids, 0)], ids.numel(), out)
         return out.view(-1)
 
+    def candidate_ids(self, x: Dict[str, Any]) -> Optional[torch.Tensor]:
+        """The batch's encoded candidate ids [B] (int32) for the loss when
+        remove_accidental_hits is set, else None.  A view of the batch's
+        column when that is an int32 device tensor already (the graphed
+        step's static word buffer): no copy, nothing to re-capture."""
+        if not self.remove_accidental_hits:
+            return None
+        ids = x[self.candidate_id_col]
+        ids = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+        return ids.reshape(-1).to(self.device, torch.int32).contiguous()
+
     def _logq_call(self, x: Dict[str, Any]):
         """(segments, out) of the logQ lookup as a 1-wide gather call, or None
         when logQ comes another way (precomputed in the batch / disabled)."""
@@ -183,16 +202,18 @@ class TwoTowerModel(AbstractKerasModel):
                     # the forward instead of landing in front of the backward
                     self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
             logq = call[1].view(-1) if call is not None else self.candidate_logq(x)
-            return self.tower_loss(qi, ci, logq)
+            return self.tower_loss(qi, ci, logq, self.candidate_ids(x))
 
-    def tower_loss(self, qi: torch.Tensor, ci: torch.Tensor, logq: Optional[torch.Tensor]) -> torch.Tensor:
+    def tower_loss(self, qi: torch.Tensor, ci: torch.Tensor, logq: Optional[torch.Tensor],
+                   ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Loss from the gathered tower inputs: with gradients, both MLPs and the
-        in-batch loss run as one autograd node (losses.towers_inbatch_softmax_xent)."""
+        in-batch loss run as one autograd node (losses.towers_inbatch_softmax_xent).
+        ids: candidate_ids(x) (accidental hits removed), or None."""
         if torch.is_grad_enabled():
             return towers_inbatch_softmax_xent(qi, ci, self.query_tower.dense, self.candidate_tower.dense, logq,
                                                self.loss.reduction, getattr(self, "_on_tower", None),
-                                               getattr(self, "_on_dx", None))
-        return self.loss(self.query_tower.dense(qi), self.candidate_tower.dense(ci), logq)
+                                               getattr(self, "_on_dx", None), ids)
+        return self.loss(self.query_tower.dense(qi), self.candidate_tower.dense(ci), logq, ids)
 
     def compile(self, loss=None, optimizer=None, **kwargs) -> None:
         """Keras-style compile: the loss must be the in-batch softmax CE

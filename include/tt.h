@@ -480,6 +480,61 @@ int tt_inbatch_softmax_xent_loss(const float* q, int64_t ldq, const float* c,
                                  int32_t prepped, void* workspace,
                                  size_t workspace_bytes, tt_stream_t stream);
 
+/* Opt-in removal of accidental hits (duplicate candidates in the batch;
+ * TensorFlow Recommenders' remove_accidental_hits).  The reference has no
+ * such option (two_tower_model.py:113-124 takes every other column as a
+ * negative): these entries depart from its loss, the entries above do not
+ * change.  With row_ids[i] / col_ids[j] the int32 candidate ids of row i and
+ * column j:
+ *
+ *   S'[i][j] = q_i . c_j - logq[j]   for j == pos(i), or col_ids[j] != row_ids[i]
+ *   S'[i][j] = -inf                  for j != pos(i) and col_ids[j] == row_ids[i]
+ *
+ * and loss_i, dq_i, dc_j as above over this S'.  A masked pair has weight 0
+ * in the rows pass (nothing to lse_i or dq_i) and in the cols pass (nothing
+ * to dc_j); the mask is the score accumulator's initial value inside the
+ * pass kernel (subtracting the duplicates' terms from lse afterwards would
+ * cancel: they equal the positive's).  The positive pair is excluded by
+ * position and added in fp32 exactly as above, whatever its ids say.  A row
+ * whose every other column is a hit has loss 0 and dq row 0 exactly and adds
+ * nothing to any dc.  Ids are compared for equality only: all
+ * out-of-vocabulary rows (id 0) count as one candidate.  With pairwise
+ * distinct ids the results equal the plain entries' bit for bit.
+ *
+ * x3 != 0: the bf16x3 products of tt_inbatch_softmax_xent_x3; otherwise the
+ * bf16 contract of K5+K6+K7.  Arguments, checks and error codes otherwise as
+ * the plain entries'; NULL ids are TT_ERR_BAD_ARG.  The workspaces are the
+ * plain ones plus the padded id vectors.  There is no split-preparation
+ * (tt_inbatch_prep) form. */
+size_t tt_inbatch_hits_workspace_size(int64_t n_rows, int64_t n_cols,
+                                      int32_t dim, int32_t x3);
+int tt_inbatch_xent_rows_hits(const float* q, int64_t ldq, int64_t n_rows,
+                              const float* c, int64_t ldc, int64_t n_cols,
+                              int32_t dim, const float* logq,
+                              int64_t pos_offset, const int32_t* row_ids,
+                              const int32_t* col_ids, int32_t x3, float* lse,
+                              float* row_loss, float* dq, void* workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+int tt_inbatch_xent_cols_hits(const float* q, int64_t ldq, int64_t n_rows,
+                              const float* lse, const float* row_loss,
+                              const float* c, int64_t ldc, int64_t n_cols,
+                              int32_t dim, const float* logq,
+                              int64_t pos_offset, const int32_t* row_ids,
+                              const int32_t* col_ids, int32_t x3, float* dc,
+                              void* workspace, size_t workspace_bytes,
+                              tt_stream_t stream);
+/* Single device (rows = cols = the batch, ids [n] serve both), with
+ * tt_inbatch_softmax_xent_loss's in-launch *loss = loss_scale *
+ * sum(row_loss) (loss may be NULL). */
+size_t tt_inbatch_fused_hits_workspace_size(int64_t n, int32_t dim, int32_t x3);
+int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const float* c,
+                                 int64_t ldc, int64_t n, int32_t dim,
+                                 const float* logq, const int32_t* ids,
+                                 int32_t x3, float* lse, float* row_loss,
+                                 float* dq, float* dc, float loss_scale,
+                                 float* loss, void* workspace,
+                                 size_t workspace_bytes, tt_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * K11+K12  Brute-force scoring with fused top-K.
  * Replaces BruteForceIndex.call (pkg/modelling/indices/brute_force.py:76-81):
