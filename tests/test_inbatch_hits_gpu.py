@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+import inbatch_rowwise
+from oracle import oracle
 from pkg.modelling import hip_ops
 
 pytestmark = pytest.mark.gpu
@@ -125,10 +127,19 @@ def _holds(e, tol):
 def _check_vs_fp64(cuda, B, E, V, scale, x3, tol):
     q, c, logq, ids, loss_ref, dq_ref, dc_ref = _inputs(cuda, B, E, V, scale)
     tag = f"{'x3' if x3 else 'bf16'} B={B} E={E} V={V}"
-    e = _errors(tag + " fused hits", hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids), loss_ref, dq_ref, dc_ref)
+    fused, sharded = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids), _sharded(q, c, logq, ids, 1, x3)
+    e = _errors(tag + " fused hits", fused, loss_ref, dq_ref, dc_ref)
     assert _holds(e, tol), e
-    e = _errors(tag + " rows+cols hits", _sharded(q, c, logq, ids, 1, x3), loss_ref, dq_ref, dc_ref)
+    e = _errors(tag + " rows+cols hits", sharded, loss_ref, dq_ref, dc_ref)
     assert _holds(e, tol), e
+    # every element within its own bound (DESIGN.md §6 "Per-element guarantees")
+    ids_np = ids.cpu().numpy()
+    con = None if x3 else oracle.inbatch_softmax_xent_bf16(q.cpu().numpy(), c.cpu().numpy(), logq.cpu().numpy(),
+                                                           row_ids=ids_np, col_ids=ids_np, aux=True)
+    for name, out in (("fused", fused), ("rows+cols", sharded)):
+        bad = (inbatch_rowwise.check_x3(out, q, c, logq, ids, f"{tag} {name}") if x3 else
+               inbatch_rowwise.check_bf16(out, q, c, logq, con, ids, f"{tag} {name}"))
+        assert not bad, "\n".join(bad)
     if len(torch.unique(ids)) < B:
         # the plain entry on the same tensors scores the duplicates as negatives
         e = _errors(tag + " fused plain", hip_ops.inbatch_fused(q, c, logq, x3=x3), loss_ref, dq_ref, dc_ref)
