@@ -1,4 +1,5 @@
-// K14 recall hits and the per-shard top-k merge; the loss reduction.
+// K14 recall hits, the per-shard top-k merge and the per-query exclusion
+// filter of sorted top-k lists; the loss reduction.
 //
 // tt_recall_hits restates IndexRecall.__call__
 // (/root/reference/pkg/modelling/metrics/index_recall.py:52-58):
@@ -126,6 +127,148 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(const float* __restrict
   }
 }
 
+// ---- tt_topk_exclude --------------------------------------------------------
+// Removes each query's excluded candidates from its sorted list and compacts
+// to k_out, in O(k_in + |E_q|) with no sort: the list's indices go into an
+// open-addressing hash table in LDS (>= 2 * k_in slots, linear probing,
+// value = list position), the exclusions are streamed one per lane and flag
+// the positions they hit, and the unflagged entries are compacted in order
+// with ballot + popcount prefixes.  The result depends only on membership,
+// so the order the LDS atomics land in does not matter.
+//
+// One group of NW waves per query: NW = 1 runs four queries per 256-thread
+// workgroup (each wave on its own LDS region, no workgroup barrier), NW = 4
+// one query per workgroup.  The switch point follows from the NW = 1 form's
+// LDS: at k_in = 256 a workgroup takes 4 x 3.3 KB, so the 160 KB of a CU
+// hold eleven workgroups and the 32-waves-per-CU cap (eight) stays the
+// limit; at 512 it would take 26 KB and LDS would cut that to six.  The
+// NW = 4 form needs at most 52 KB (k_in = 4096): three workgroups per CU.
+constexpr int32_t kPadIndex = 0x7FFFFFFF;
+constexpr int kExcludeSmallK = 256;
+constexpr int kExcludeMaxK = 4096;
+
+template <int NW>
+__device__ __forceinline__ void group_sync() {
+  if constexpr (NW == 1) {
+    // a wave's LDS operations execute in order; this keeps the compiler from moving them across
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
+// LDS of one group: table [1 << log2p] int, list indices [k_in] int32, flags
+// [k_in] bytes, then (16-B aligned) the per-wave kept counts.
+inline int exclude_group_bytes(int k_in, int log2p) {
+  return static_cast<int>(round_up((int64_t{1} << log2p) * 4 + k_in * 4ll + k_in, 16)) + 16;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(256) topk_exclude_kernel(const float* __restrict__ scores,
+                                                           const int32_t* __restrict__ idx, int64_t n_queries,
+                                                           int k_in, int k_out, const int64_t* __restrict__ excl_off,
+                                                           const int32_t* __restrict__ excl_idx,
+                                                           float* __restrict__ out_s, int32_t* __restrict__ out_i,
+                                                           int32_t* __restrict__ n_kept, int log2p, int group_bytes) {
+  extern __shared__ __align__(16) unsigned char exclude_lds[];
+  constexpr int NT = NW * kWave;
+  const int wave = static_cast<int>(threadIdx.x) / kWave;
+  const int lane = lane_id();
+  const int64_t q = NW == 1 ? blockIdx.x * 4ll + wave : static_cast<int64_t>(blockIdx.x);
+  if (q >= n_queries) return;  // NW = 1 only: a whole wave, and no workgroup barrier follows
+  const int t = NW == 1 ? lane : static_cast<int>(threadIdx.x);
+  const float* ls = scores + q * k_in;
+  const int32_t* li = idx + q * k_in;
+  float* os = out_s + q * k_out;
+  int32_t* oi = out_i + q * k_out;
+  const int64_t eb = excl_off[q], ee = excl_off[q + 1];
+  if (ee <= eb) {  // nothing to exclude (uniform over the group): the first k_out entries as they are
+    for (int j = t; j < k_out; j += NT) {
+      os[j] = ls[j];
+      oi[j] = li[j];
+    }
+    if (t == 0 && n_kept) n_kept[q] = k_out;
+    return;
+  }
+  unsigned char* base = exclude_lds + (NW == 1 ? wave * group_bytes : 0);
+  const int P = 1 << log2p;
+  int* table = reinterpret_cast<int*>(base);
+  int32_t* lidx = table + P;
+  unsigned char* flag = reinterpret_cast<unsigned char*>(lidx + k_in);
+  int* wcnt = reinterpret_cast<int*>(base + group_bytes - 16);
+  const unsigned mask = static_cast<unsigned>(P - 1);
+  const int shift = 32 - log2p;  // log2p >= 1
+  auto slot_of = [&](int32_t v) { return (static_cast<unsigned>(v) * 2654435761u) >> shift; };
+
+  for (int j = t; j < P; j += NT) table[j] = -1;
+  for (int j = t; j < k_in; j += NT) {
+    lidx[j] = li[j];
+    flag[j] = 0;
+  }
+  group_sync<NW>();
+  // at most k_in inserts into >= 2 * k_in slots: every probe sequence ends
+  for (int j = t; j < k_in; j += NT) {
+    const int32_t v = lidx[j];
+    if (v == kPadIndex) continue;
+    unsigned s = slot_of(v);
+    while (atomicCAS(&table[s], -1, j) != -1) s = (s + 1) & mask;
+  }
+  group_sync<NW>();
+  for (int64_t e = eb + t; e < ee; e += NT) {
+    const int32_t v = excl_idx[e];
+    if (v < 0 || v == kPadIndex) continue;  // match nothing
+    unsigned s = slot_of(v);
+    for (;;) {
+      const int p = table[s];
+      if (p < 0) break;
+      if (lidx[p] == v) flag[p] = 1;  // on to the empty slot: a repeated list index is flagged too
+      s = (s + 1) & mask;
+    }
+  }
+  group_sync<NW>();
+
+  // each wave compacts one contiguous segment of the list
+  const int seg = ((k_in + NW - 1) / NW + kWave - 1) / kWave * kWave;
+  const int sb = NW == 1 ? 0 : wave * seg;
+  const int se = sb + seg < k_in ? sb + seg : k_in;
+  const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int n = 0, total = 0;
+  if constexpr (NW > 1) {
+    int cnt = 0;
+    for (int j0 = sb; j0 < se; j0 += kWave) {
+      const int j = j0 + lane;
+      cnt += __popcll(__ballot(j < se && !flag[j]));
+    }
+    if (lane == 0) wcnt[wave] = cnt;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const int c = wcnt[w];
+      n += w < wave ? c : 0;
+      total += c;
+    }
+  }
+  for (int j0 = sb; j0 < se && n < k_out; j0 += kWave) {
+    const int j = j0 + lane;
+    const bool keep = j < se && !flag[j];
+    const uint64_t m = __ballot(keep);
+    const int p = n + __popcll(m & lt);
+    if (keep && p < k_out) {
+      os[p] = ls[j];
+      oi[p] = lidx[j];
+    }
+    n += __popcll(m);
+  }
+  if constexpr (NW == 1) total = n;  // stops counting at k_out: min(k_out, .) below is unaffected
+  const int kept = total < k_out ? total : k_out;
+  for (int j = kept + t; j < k_out; j += NT) {
+    os[j] = -INFINITY;
+    oi[j] = kPadIndex;
+  }
+  if (t == 0 && n_kept) n_kept[q] = kept;
+}
+
 }  // namespace
 }  // namespace tt
 
@@ -175,6 +318,31 @@ extern "C" int tt_topk_merge(const float* scores, const int32_t* idx, int32_t nu
   TT_REQUIRE(scores && idx && out_scores && out_idx, "tt_topk_merge: NULL pointer");
   hipLaunchKernelGGL(topk_merge_kernel, dim3(ceil_div(n_queries, 4)), dim3(256), 0, to_stream(stream), scores, idx,
                      num_lists, n_queries, k_in, k_out, out_scores, out_idx);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int tt_topk_exclude(const float* scores, const int32_t* idx, int64_t n_queries, int32_t k_in,
+                               int32_t k_out, const int64_t* excl_off, const int32_t* excl_idx, float* out_scores,
+                               int32_t* out_idx, int32_t* n_kept, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(k_out >= 1 && k_out <= k_in && k_in <= kExcludeMaxK,
+             "tt_topk_exclude: need 1 <= k_out <= k_in <= %d (got k_in=%d, k_out=%d)", kExcludeMaxK, k_in, k_out);
+  TT_REQUIRE(n_queries >= 0 && n_queries <= INT32_MAX, "tt_topk_exclude: n_queries outside [0, 2^31)");
+  if (n_queries == 0) return TT_OK;
+  TT_REQUIRE(scores && idx && excl_off && out_scores && out_idx, "tt_topk_exclude: NULL pointer");
+  int log2p = 1;
+  while ((1 << log2p) < 2 * k_in) ++log2p;
+  const int group_bytes = exclude_group_bytes(k_in, log2p);
+  if (k_in <= kExcludeSmallK) {
+    hipLaunchKernelGGL(topk_exclude_kernel<1>, dim3(ceil_div(n_queries, 4)), dim3(256), 4 * group_bytes,
+                       to_stream(stream), scores, idx, n_queries, k_in, k_out, excl_off, excl_idx, out_scores,
+                       out_idx, n_kept, log2p, group_bytes);
+  } else {
+    hipLaunchKernelGGL(topk_exclude_kernel<4>, dim3(n_queries), dim3(256), group_bytes, to_stream(stream), scores,
+                       idx, n_queries, k_in, k_out, excl_off, excl_idx, out_scores, out_idx, n_kept, log2p,
+                       group_bytes);
+  }
   TT_CHECK_LAUNCH();
   return TT_OK;
 }

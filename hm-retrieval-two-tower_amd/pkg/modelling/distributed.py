@@ -100,6 +100,10 @@ class IndexOps:
     shard_search: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor]]] = None
     # (n_queries, shard sizes of ALL ranks, dim, k) -> the common query chunk
     shard_chunk: Optional[Callable[[int, Sequence[int], int, int], int]] = None
+    # (scores [Q, k_in], idx [Q, k_in], excl_off [Q + 1], excl_idx, k_out) ->
+    # (scores [Q, k_out], idx [Q, k_out], n_kept [Q]): the sorted lists without
+    # each query's excluded indices (tt_topk_exclude); None: hip_ops.topk_exclude
+    exclude: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]] = None
 
     @staticmethod
     def hip() -> "IndexOps":
@@ -107,7 +111,15 @@ class IndexOps:
 
         return IndexOps(hip_ops.bruteforce_build,
                         lambda img, cand, q, k, off: hip_ops.bruteforce_search(img, cand, q, k, off),
-                        hip_ops.topk_merge, hip_ops.bruteforce_shard_search, hip_ops.bruteforce_shard_chunk)
+                        hip_ops.topk_merge, hip_ops.bruteforce_shard_search, hip_ops.bruteforce_shard_chunk,
+                        hip_ops.topk_exclude)
+
+    def excluder(self) -> Callable[..., Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        if self.exclude is not None:
+            return self.exclude
+        from pkg.modelling import hip_ops
+
+        return hip_ops.topk_exclude
 
 
 def _staged(group) -> bool:
@@ -246,12 +258,18 @@ class ShardedBruteForceIndex:
             s, i = ps, pi
         return s, i
 
-    def search_owned(self, query_embeddings: torch.Tensor, k: Optional[int] = None
+    def search_owned(self, query_embeddings: torch.Tensor, k: Optional[int] = None, exclusions=None
                      ) -> Tuple[Tuple[int, int], torch.Tensor, torch.Tensor]:
         """Exact global top-k of this rank's query block: ((begin, end),
-        scores [end-begin, k], indices [end-begin, k] int32)."""
+        scores [end-begin, k], indices [end-begin, k] int32).  exclusions: as
+        for search(); the block is then cut from search()'s all-gathered
+        answer, because the classes' query blocks are not the batch's."""
         k = k or self.k
         Q, G = int(query_embeddings.shape[0]), self.world
+        if exclusions is not None:
+            s, i = self.search(query_embeddings, k, exclusions)
+            b, e = shard_range(Q, G, self.rank)
+            return (b, e), s[b:e], i[b:e]
         s, i = self.search_shard(query_embeddings, k)
         blocks = [shard_range(Q, G, r) for r in range(G)]
         mb, me = blocks[self.rank]
@@ -268,17 +286,47 @@ class ShardedBruteForceIndex:
         ms, mi = self.ops.merge(rs.view(G, nb, k), ri.view(G, nb, k), k)
         return (mb, me), ms, mi
 
-    def search(self, query_embeddings: torch.Tensor, k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Global (scores [Q,k], indices [Q,k]) on every rank (blocks all-gathered)."""
+    def search(self, query_embeddings: torch.Tensor, k: Optional[int] = None,
+               exclusions=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Global (scores [Q,k], indices [Q,k]) on every rank (blocks all-gathered).
+
+        exclusions: per-query GLOBAL candidate positions that must not be
+        returned (indices.exclusions.as_csr forms), replicated on every rank
+        like the queries.  The classes (exclusions.plan_classes) are computed
+        from the replicated counts, so every rank runs the same sequence of
+        searches and collectives: per class the shard search, all_to_all and
+        merge at k' = k + the class's largest count, then the owner filters
+        its query block to k (tt_topk_exclude) before the all-gather.  Exact:
+        the merged list is the global top-k', and removing at most k' - k of
+        its entries leaves the top-k of the rest in the same order."""
         Q = int(query_embeddings.shape[0])
+        if exclusions is not None:
+            from pkg.modelling.indices import exclusions as excl
+
+            k = k or self.k
+
+            def run(qc, k_search, off, idx, count):
+                (b, e), s, i = self.search_owned(qc, k_search)
+                if count:
+                    if e > b:  # the kernel reads excl_idx[off[q]:off[q+1]]: the block's offsets into the whole idx
+                        s, i, _ = self.ops.excluder()(s.contiguous(), i.contiguous(), off[b:e + 1].contiguous(), idx, k)
+                    else:
+                        s, i = s[:, :k], i[:, :k]
+                if self.world == 1:
+                    return s, i
+                return _gather_query_blocks(s, i, int(qc.shape[0]), self.world, self.group)
+
+            return excl.run_classes(query_embeddings.contiguous(), k, self.num_candidates, exclusions, run)
         _, s, i = self.search_owned(query_embeddings, k)
         if self.world == 1:
             return s, i
         return _gather_query_blocks(s, i, Q, self.world, self.group)
 
-    def __call__(self, queries: Dict[str, Any]):
+    def __call__(self, queries: Dict[str, Any], exclusions=None):
         with torch.no_grad():
             emb = self.query_model(queries)
+        if exclusions is not None:
+            return self.search(emb, exclusions=exclusions)[1]
         return self.search(emb)[1]
 
 
@@ -309,23 +357,46 @@ class QueryShardedBruteForceIndex:
         self.image = self.ops.build(self.cand)
         self.identifiers = identifiers
 
-    def search_owned(self, query_embeddings: torch.Tensor, k: Optional[int] = None
+    def search_owned(self, query_embeddings: torch.Tensor, k: Optional[int] = None, exclusions=None
                      ) -> Tuple[Tuple[int, int], torch.Tensor, torch.Tensor]:
-        """((begin, end), scores [end-begin, k], indices) of this rank's query block."""
+        """((begin, end), scores [end-begin, k], indices) of this rank's query
+        block.  exclusions: per-query candidate positions of ALL queries
+        (indices.exclusions.as_csr forms); this rank plans and filters the
+        exclusions of its own block (no collective is involved)."""
         k = k or self.k
-        b, e = shard_range(int(query_embeddings.shape[0]), self.world, self.rank)
+        Q = int(query_embeddings.shape[0])
+        b, e = shard_range(Q, self.world, self.rank)
+        if exclusions is not None:
+            from pkg.modelling.indices import exclusions as excl
+
+            off, idx, _ = excl.as_csr(exclusions, Q)
+            lo, hi = int(off[b]), int(off[e])
+
+            def run(qc, k_search, coff, cidx, count):
+                s, i = self.ops.search(self.image, self.cand, qc, k_search, 0)
+                return (s, i) if count == 0 else self.ops.excluder()(s, i, coff, cidx, k)[:2]
+
+            s, i = excl.run_classes(query_embeddings[b:e].contiguous(), k, self.num_candidates,
+                                    (off[b:e + 1] - lo, idx[lo:hi]), run)
+            return (b, e), s, i
         s, i = self.ops.search(self.image, self.cand, query_embeddings[b:e].contiguous(), k, 0)
         return (b, e), s, i
 
-    def search(self, query_embeddings: torch.Tensor, k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, query_embeddings: torch.Tensor, k: Optional[int] = None,
+               exclusions=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Global (scores [Q,k], indices [Q,k]) on every rank (blocks all-gathered)."""
         Q = int(query_embeddings.shape[0])
-        _, s, i = self.search_owned(query_embeddings, k)
+        if exclusions is not None:
+            _, s, i = self.search_owned(query_embeddings, k, exclusions)
+        else:
+            _, s, i = self.search_owned(query_embeddings, k)
         return _gather_query_blocks(s, i, Q, self.world, self.group)
 
-    def __call__(self, queries: Dict[str, Any]):
+    def __call__(self, queries: Dict[str, Any], exclusions=None):
         with torch.no_grad():
             emb = self.query_model(queries)
+        if exclusions is not None:
+            return self.search(emb, exclusions=exclusions)[1]
         return self.search(emb)[1]
 
 

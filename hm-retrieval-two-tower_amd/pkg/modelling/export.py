@@ -208,9 +208,19 @@ class Retriever:
     def encode(self, queries: Dict[str, Any]) -> Dict[str, torch.Tensor]:
         return self.tower.input_layer.encode(queries)
 
-    def __call__(self, queries: Dict[str, Any], k: Optional[int] = None, scores: bool = False):
+    def __call__(self, queries: Dict[str, Any], k: Optional[int] = None, scores: bool = False, exclude=None):
+        """exclude: per-query raw identifiers that must not be returned (e.g.
+        the articles a customer already has): a list of per-query lists;
+        strings for a string-identified index, compared as str() like the
+        query features; identifiers the index does not hold are ignored.  The
+        result is the exact top-k of the remaining candidates
+        (BruteForceIndex.query_with_exclusions)."""
         with torch.no_grad():
             emb = self.tower(self.encode(queries))
-            s, idx = self.index.search(emb, k)
+            if exclude is None:
+                s, idx = self.index.search(emb, k)
+            else:
+                pos = self.index.exclusion_positions(exclude, int(emb.shape[0]), k)
+                s, idx = self.index.search(emb, k, exclusions=pos)
         ids = self.index.lookup_identifiers(idx)
         return (ids, s) if scores else ids

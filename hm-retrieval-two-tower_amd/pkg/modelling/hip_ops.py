@@ -45,6 +45,7 @@ __all__ = [
     "bruteforce_search",
     "bruteforce_shard_search",
     "topk_merge",
+    "topk_exclude",
     "recall_hits",
     "Workspace",
     "capture_guard",
@@ -1083,6 +1084,39 @@ def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k_out: int) -> Tuple[tor
     check(lib().tt_topk_merge(scores.data_ptr(), idx.data_ptr(), Ln, Q, k_in, k_out, out_s.data_ptr(),
                               out_i.data_ptr(), _stream()))
     return out_s, out_i
+
+
+def topk_exclude(scores: torch.Tensor, idx: torch.Tensor, excl_off: torch.Tensor, excl_idx: torch.Tensor,
+                 k_out: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sorted lists scores/idx [Q, k_in] without each query's excluded
+    candidates, compacted to k_out (tt_topk_exclude): query q's exclusions
+    are excl_idx[excl_off[q]:excl_off[q+1]] (excl_off int64 [Q+1], device,
+    non-decreasing, every offset within excl_idx — not checked here, that
+    would synchronise; excl_idx int32, any order).  Returns (scores [Q, k_out],
+    idx [Q, k_out], n_kept [Q] int32); rows with fewer than k_out entries left
+    are padded with (-inf, INT32_MAX)."""
+    _req(scores, "scores", torch.float32, 2)
+    _req(idx, "idx", torch.int32, 2)
+    _req(excl_off, "excl_off", torch.int64, 1)
+    _req(excl_idx, "excl_idx", torch.int32, 1)
+    if not (scores.is_contiguous() and idx.is_contiguous()) or scores.shape != idx.shape:
+        raise ValueError("scores/idx must be contiguous and of equal shape")
+    Q, k_in = scores.shape
+    if excl_off.numel() != Q + 1 or not (excl_off.is_contiguous() and excl_idx.is_contiguous()):
+        raise ValueError(f"excl_off must be a contiguous [{Q + 1}] int64 tensor and excl_idx contiguous")
+    for t, name in ((idx, "idx"), (excl_off, "excl_off"), (excl_idx, "excl_idx")):
+        if t.device != scores.device:
+            raise ValueError(f"{name} must live on the scores' device {scores.device} (got {t.device})")
+    k_out = int(k_out)
+    if not 1 <= k_out <= k_in:
+        raise ValueError(f"need 1 <= k_out <= k_in = {k_in}, got k_out={k_out}")
+    out_s = torch.empty(Q, k_out, dtype=torch.float32, device=scores.device)
+    out_i = torch.empty(Q, k_out, dtype=torch.int32, device=scores.device)
+    kept = torch.empty(Q, dtype=torch.int32, device=scores.device)
+    check(lib().tt_topk_exclude(scores.data_ptr(), idx.data_ptr(), Q, k_in, k_out, excl_off.data_ptr(),
+                                excl_idx.data_ptr() if excl_idx.numel() else None, out_s.data_ptr(),
+                                out_i.data_ptr(), kept.data_ptr(), _stream()))
+    return out_s, out_i, kept
 
 
 def recall_hits(true_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int], hits: torch.Tensor) -> None:

@@ -57,8 +57,10 @@ class IndexRecall:
             for k in self.ks:
                 self._host_hits[k] += int(eq[:, :k].sum())
 
-    def __call__(self, queries: Dict[str, Any], true_candidate_ids) -> Dict[int, np.float64]:
-        candidates = self.index(queries)
+    def __call__(self, queries: Dict[str, Any], true_candidate_ids, exclusions=None) -> Dict[int, np.float64]:
+        """exclusions: per-query identifiers the index must leave out (recall
+        on unseen items), forwarded as index(queries, exclusions=...)."""
+        candidates = self.index(queries) if exclusions is None else self.index(queries, exclusions=exclusions)
         n = true_candidate_ids.shape[0] if hasattr(true_candidate_ids, "shape") else len(true_candidate_ids)
         self.seen += int(n)
         self._update(true_candidate_ids, candidates)

@@ -608,6 +608,37 @@ int tt_topk_merge(const float* scores, const int32_t* idx, int32_t num_lists,
                   int64_t n_queries, int32_t k_in, int32_t k_out,
                   float* out_scores, int32_t* out_idx, tt_stream_t stream);
 
+/* Exact top-k with per-query exclusions (TensorFlow Recommenders'
+ * query_with_exclusions): remove each query's excluded candidates from its
+ * sorted list and compact to k_out.  scores / idx are [n_queries][k_in],
+ * sorted as tt_bruteforce_search and tt_topk_merge write them; query q's
+ * exclusions are E_q = excl_idx[excl_off[q] .. excl_off[q + 1]) (candidate
+ * indices in the lists' numbering, any order; excl_off is device int64
+ * [n_queries + 1], non-decreasing, and every offset lies inside excl_idx).
+ *   - Output row q holds the input entries, in input order, whose index is
+ *     not in E_q; only the first k_out of them are written.  Scores and
+ *     indices are copied, never recomputed.  Run on the exact top-(k +
+ *     |E_q|) this leaves the exact top-k of the remaining candidates in the
+ *     same order (score descending, ties to the lower index).
+ *   - Positions past the kept entries hold (-inf, 0x7FFFFFFF), the padding
+ *     tt_bruteforce_shard_finalize writes and tt_topk_merge sorts last.
+ *   - n_kept (int32 [n_queries], or NULL) receives min(k_out, kept entries).
+ *   - E_q may be empty, longer than k_in (no upper bound), unordered, and
+ *     may hold duplicates and values that are not in the list; negative
+ *     values and 0x7FFFFFFF match nothing, so an input padding entry
+ *     (idx == 0x7FFFFFFF) is never removed: it counts as a kept entry and
+ *     stays at the tail.
+ *   - The outputs must not overlap the inputs.
+ * Needs 1 <= k_out <= k_in <= 4096 and n_queries >= 0 (0: TT_OK, no launch);
+ * every pointer but n_kept non-NULL when n_queries > 0, except that excl_idx
+ * may be NULL when the caller guarantees that every list is empty
+ * (excl_off[q] == excl_off[q + 1] for all q).  One launch, O(k_in + |E_q|)
+ * per query, no workspace. */
+int tt_topk_exclude(const float* scores, const int32_t* idx, int64_t n_queries,
+                    int32_t k_in, int32_t k_out, const int64_t* excl_off,
+                    const int32_t* excl_idx, float* out_scores, int32_t* out_idx,
+                    int32_t* n_kept, tt_stream_t stream);
+
 /* The in-batch loss's batch reduction (CategoricalCrossentropy reduction
  * SUM, runner.py:78-83): out[0] = scale * sum(x[0..n)), one deterministic
  * single-workgroup launch. */
