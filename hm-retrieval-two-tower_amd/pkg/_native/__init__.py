@@ -23,6 +23,8 @@ __all__ = [
     "MlpPackJob",
     "MlpRowsProblem",
     "MlpWgradProblem",
+    "L2NormJob",
+    "L2NormGradJob",
     "MAX_SEGMENTS",
     "MAX_SOURCES",
     "lib",
@@ -130,6 +132,34 @@ class MlpWgradProblem(ctypes.Structure):
         ("Ka", c_int32),
         ("N", c_int32),
         ("dwb", c_void_p),
+    ]
+
+
+class L2NormJob(ctypes.Structure):
+    _fields_ = [
+        ("x", c_void_p),
+        ("ldx", c_int64),
+        ("y", c_void_p),
+        ("ldy", c_int64),
+        ("inv", c_void_p),
+        ("rows", c_int64),
+        ("dim", c_int32),
+        ("scale", c_float),
+    ]
+
+
+class L2NormGradJob(ctypes.Structure):
+    _fields_ = [
+        ("x", c_void_p),
+        ("ldx", c_int64),
+        ("inv", c_void_p),
+        ("dy", c_void_p),
+        ("lddy", c_int64),
+        ("dx", c_void_p),
+        ("lddx", c_int64),
+        ("rows", c_int64),
+        ("dim", c_int32),
+        ("scale", c_float),
     ]
 
 
@@ -360,6 +390,8 @@ _PROTOS = {
         c_int32,
         [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
          c_void_p]),
+    "tt_l2norm_rows": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "tt_l2norm_rows_grad": (c_int32, [c_void_p, c_int32, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

@@ -91,7 +91,9 @@ def _device(device) -> torch.device:
 # ---- towers -----------------------------------------------------------------
 def _tower_meta(tower) -> dict:
     return {"kind": "tower", "features": [_feature_spec(f) for f in tower.features],
-            "joint_embedding_size": tower.joint_embedding_size, "hidden_units": tower.hidden_units}
+            "joint_embedding_size": tower.joint_embedding_size, "hidden_units": tower.hidden_units,
+            # cosine scoring (files written before these fields load as False, 1.0)
+            "normalize": bool(tower.normalize), "output_scale": float(tower.output_scale)}
 
 
 def save_tower(tower, path_noext: str) -> None:
@@ -103,7 +105,8 @@ def _build_tower(meta: dict, tensors, arrays, device, prefix: str = ""):
     from pkg.modelling.models.tower import Tower
 
     feats = _features_from(meta["features"], arrays, "")
-    tower = Tower(feats, meta["joint_embedding_size"], meta["hidden_units"], device)
+    tower = Tower(feats, meta["joint_embedding_size"], meta["hidden_units"], device,
+                  normalize=bool(meta.get("normalize", False)), output_scale=float(meta.get("output_scale", 1.0)))
     tower.load_state_dict({k[len(prefix):]: v for k, v in tensors.items() if k.startswith(prefix)})
     return tower
 
@@ -124,7 +127,8 @@ def save_two_tower(model, path_noext: str) -> None:
             "joint_embedding_size": model.query_tower.joint_embedding_size,
             "query_tower_units": model.query_tower.hidden_units,
             "candidate_tower_units": model.candidate_tower.hidden_units,
-            "remove_accidental_hits": bool(model.remove_accidental_hits)}
+            "remove_accidental_hits": bool(model.remove_accidental_hits),
+            "normalize_embeddings": bool(model.normalize_embeddings), "temperature": model.temperature}
     arrays = _vocab_arrays(model.query_features, "query.")
     arrays.update(_vocab_arrays(model.candidate_features, "candidate."))
     arrays["logq.keys"] = np.asarray(list(lookup.keys()), dtype=str)
@@ -144,7 +148,9 @@ def load_two_tower(path_noext: str, device=None):
                           _features_from(meta["candidate_features"], arrays, "candidate."),
                           meta["candidate_id_col"], meta["joint_embedding_size"], meta["query_tower_units"],
                           meta["candidate_tower_units"], candidate_prob_lookup=lookup, device=_device(device),
-                          remove_accidental_hits=bool(meta.get("remove_accidental_hits", False)))
+                          remove_accidental_hits=bool(meta.get("remove_accidental_hits", False)),
+                          normalize_embeddings=bool(meta.get("normalize_embeddings", False)),
+                          temperature=meta.get("temperature"))
     model.query_tower.load_state_dict({k[len("query_tower."):]: v for k, v in tensors.items()
                                        if k.startswith("query_tower.")})
     model.candidate_tower.load_state_dict({k[len("candidate_tower."):]: v for k, v in tensors.items()

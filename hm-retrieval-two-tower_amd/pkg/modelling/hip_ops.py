@@ -34,6 +34,8 @@ __all__ = [
     "inbatch_fused",
     "inbatch_fused_workspace",
     "inbatch_prep",
+    "l2norm_rows",
+    "l2norm_rows_grad",
     "probe_arm",
     "probe_arm_repeat",
     "route_requests",
@@ -1385,3 +1387,95 @@ def mlp_wgrad_pair(problems: Sequence[dict]) -> None:
         q.scale, q.M, q.Ka, q.N, q.dwb = _ptr(p.get("scale")), M, Ka, N, dwb.data_ptr()
     ws = Workspace.get(lib().tt_mlp_wgrad_pair_workspace_size(arr), problems[0]["a"].device, "mlp_wgrad")
     check(lib().tt_mlp_wgrad_pair(arr, ws.data_ptr(), ws.numel(), _stream()))
+
+
+# --------------------------------------------------------------------------
+# Cosine scoring: row L2 normalisation and its gradient
+# --------------------------------------------------------------------------
+def _norm_operand(t: torch.Tensor, name: str, rows: int, dim: int, like: torch.Tensor) -> int:
+    """A [rows, dim] fp32 operand on like's device; returns its leading dimension."""
+    _req(t, name, torch.float32, 2)
+    if tuple(t.shape) != (rows, dim):
+        raise ValueError(f"{name} must be [{rows}, {dim}], got {tuple(t.shape)}")
+    if t.device != like.device:
+        raise ValueError(f"{name} must live on {like.device} (got {t.device})")
+    return _norm_ld(t, name)
+
+
+def _norm_ld(t: torch.Tensor, name: str) -> int:
+    """_row_major, refusing rows that overlap (a row stride below the width)."""
+    ld = _row_major(t, name)
+    if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+        raise ValueError(f"{name}: row stride {t.stride(0)} below its width {t.shape[1]}")
+    return ld
+
+
+def _norm_inv(t: torch.Tensor, name: str, rows: int, like: torch.Tensor) -> None:
+    _req(t, name, torch.float32, 1)
+    if t.numel() != rows or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{name} must be a contiguous [{rows}] float32 tensor on {like.device}")
+
+
+def _norm_dim(x: torch.Tensor, name: str) -> Tuple[int, int]:
+    _req(x, name, torch.float32, 2)
+    rows, dim = x.shape
+    if not 1 <= dim <= 4096:
+        raise ValueError(f"{name}: dim={dim} outside 1..4096 (tt_l2norm_rows)")
+    return rows, dim
+
+
+def l2norm_rows(jobs: Sequence[tuple]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """Row L2 normalisation of 1 or 2 operands in ONE launch (tt_l2norm_rows).
+    Each job is (x, scale) or (x, scale, y, inv): x [rows, dim] fp32 with unit
+    column stride (any row stride >= dim), y like x and inv [rows] contiguous
+    (allocated when omitted or None).  y_i = x_i * scale / ||x_i||, inv_i =
+    1 / ||x_i||; a zero row gives y_i = 0, inv_i = 0.  Returns [(y, inv)] per
+    job.  A two-job call equals two one-job calls bit for bit."""
+    if not 1 <= len(jobs) <= 2:
+        raise ValueError("l2norm_rows takes 1 or 2 jobs")
+    arr = (_native.L2NormJob * len(jobs))()
+    out = []
+    for i, job in enumerate(jobs):
+        x, scale, y, inv = (tuple(job) + (None, None))[:4]
+        rows, dim = _norm_dim(x, f"x[{i}]")
+        ldx = _norm_ld(x, f"x[{i}]")
+        if y is None:
+            y = torch.empty(rows, dim, dtype=torch.float32, device=x.device)
+        if inv is None:
+            inv = torch.empty(rows, dtype=torch.float32, device=x.device)
+        ldy = _norm_operand(y, f"y[{i}]", rows, dim, x)
+        _norm_inv(inv, f"inv[{i}]", rows, x)
+        q = arr[i]
+        q.x, q.ldx, q.y, q.ldy, q.inv = x.data_ptr(), ldx, y.data_ptr(), ldy, inv.data_ptr()
+        q.rows, q.dim, q.scale = rows, dim, float(scale)
+        out.append((y, inv))
+    check(lib().tt_l2norm_rows(arr, len(jobs), _stream()))
+    return out
+
+
+def l2norm_rows_grad(jobs: Sequence[tuple]) -> List[torch.Tensor]:
+    """Gradient of l2norm_rows for 1 or 2 operands in ONE launch
+    (tt_l2norm_rows_grad).  Each job is (x, inv, dy, scale) or (x, inv, dy,
+    scale, dx): x the forward's input, inv its reciprocal norms, dy [rows,
+    dim] the gradient with respect to y; dx may be dy itself (in place) and is
+    allocated when omitted or None.  dx_i = scale inv_i (dy_i - u_i (u_i .
+    dy_i)) with u_i = x_i inv_i; zero rows get dx_i = 0.  Returns [dx] per job."""
+    if not 1 <= len(jobs) <= 2:
+        raise ValueError("l2norm_rows_grad takes 1 or 2 jobs")
+    arr = (_native.L2NormGradJob * len(jobs))()
+    out = []
+    for i, job in enumerate(jobs):
+        x, inv, dy, scale, dx = (tuple(job) + (None,))[:5]
+        rows, dim = _norm_dim(x, f"x[{i}]")
+        ldx = _norm_ld(x, f"x[{i}]")
+        _norm_inv(inv, f"inv[{i}]", rows, x)
+        lddy = _norm_operand(dy, f"dy[{i}]", rows, dim, x)
+        if dx is None:
+            dx = torch.empty(rows, dim, dtype=torch.float32, device=x.device)
+        lddx = _norm_operand(dx, f"dx[{i}]", rows, dim, x)
+        q = arr[i]
+        q.x, q.ldx, q.inv, q.dy, q.lddy = x.data_ptr(), ldx, inv.data_ptr(), dy.data_ptr(), lddy
+        q.dx, q.lddx, q.rows, q.dim, q.scale = dx.data_ptr(), lddx, rows, dim, float(scale)
+        out.append(dx)
+    check(lib().tt_l2norm_rows_grad(arr, len(jobs), _stream()))
+    return out

@@ -118,6 +118,34 @@ def _pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, on_tower=None):
     return gqi, gci, gflat_q, gflat_c
 
 
+def normalized_outputs(stack_q, stack_c, q: torch.Tensor, c: torch.Tensor):
+    """(q', c', invs): the two towers' joined outputs as the loss takes them.
+    A stack with normalize set has its rows L2-normalised and multiplied by
+    its output_scale (cosine scoring; the query side's scale is 1 /
+    temperature) — ONE tt_l2norm_rows launch for both operands; invs holds
+    each normalised operand's reciprocal row norms (None for one left as it
+    is).  Without normalisation: (q, c, (None, None)) and no launch."""
+    sides = [i for i, st in enumerate((stack_q, stack_c)) if st.normalize]
+    out, invs = [q, c], [None, None]
+    if sides:
+        res = hip_ops.l2norm_rows([((q, c)[i], (stack_q, stack_c)[i].output_scale) for i in sides])
+        for i, (y, inv) in zip(sides, res):
+            out[i], invs[i] = y, inv
+    return out[0], out[1], tuple(invs)
+
+
+def unnormalize_grads(stack_q, stack_c, q: torch.Tensor, c: torch.Tensor, invs, dq: torch.Tensor,
+                      dc: torch.Tensor) -> None:
+    """dq, dc (the loss's gradients with respect to normalized_outputs' q',
+    c') turned IN PLACE into the gradients with respect to the un-normalised
+    q, c: ONE tt_l2norm_rows_grad launch for both.  It is linear in dq / dc,
+    so the backward's device scalar applies afterwards as before."""
+    jobs = [(x, inv, d, st.output_scale, d)
+            for st, x, inv, d in ((stack_q, q, invs[0], dq), (stack_c, c, invs[1], dc)) if inv is not None]
+    if jobs:
+        hip_ops.l2norm_rows_grad(jobs)
+
+
 class _TowerFork:
     """Work in this block runs on the candidate tower's stream (forked from the
     current one) and workspace scope; plain on CPU tensors."""
@@ -175,8 +203,10 @@ class _TowersInBatchXent(torch.autograd.Function):
         side = _tower_stream(qi.device)
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
-        # (not under x3_scores() or with ids: those entries prepare their operands themselves)
-        split_prep = SPLIT_PREP and not x3_scores() and ids is None
+        # (not under x3_scores() or with ids: those entries prepare their operands themselves;
+        # not with normalised outputs: it would prepare the un-normalised ones)
+        split_prep = (SPLIT_PREP and not x3_scores() and ids is None
+                      and not (stack_q.normalize or stack_c.normalize))
         ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
         with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
@@ -196,19 +226,19 @@ class _TowersInBatchXent(torch.autograd.Function):
         ctx.nq = len(qa)
         ctx.scale = scale
         ctx.on_tower = on_tower
+        # cosine scoring: the loss entries run unchanged on the normalised
+        # outputs (one launch for both), and its gradients are taken back to
+        # the un-normalised ones right after it (one launch, in place)
+        q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])
         if ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, loss_scale=scale, x3=x3_scores(),
-                                                       ids=ids)
-            ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
-            return loss
-        if x3_scores():  # fp32-faithful scores (its own preparation and workspace)
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, loss_scale=scale, x3=True)
-            ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
-            return loss
-        # the loss summed by an extra workgroup of the loss entry's last launch
-        # (tt_inbatch_softmax_xent_loss): no tt_sum launch after it
-        _, _, dq, dc, loss = hip_ops.inbatch_fused(qa[-1], ca[-1], logq, ws=ws, prepped=ws is not None,
-                                                   loss_scale=scale)
+            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids)
+        elif x3_scores():  # fp32-faithful scores (its own preparation and workspace)
+            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=True)
+        else:
+            # the loss summed by an extra workgroup of the loss entry's last launch
+            # (tt_inbatch_softmax_xent_loss): no tt_sum launch after it
+            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, ws=ws, prepped=ws is not None, loss_scale=scale)
+        unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
         ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
         return loss
 
@@ -302,7 +332,9 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
                 ca = stack_c.forward_acts(ci, flat_c)
             qa = stack_q.forward_acts(qi, flat_q)
             _tower_join(qi)
-        row_loss, dq, dc = global_inbatch_grads(qa[-1], ca[-1], logq, comm, ids=ids)
+        q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])  # cosine scoring (as _TowersInBatchXent)
+        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids)
+        unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
         ctx.scale = scale

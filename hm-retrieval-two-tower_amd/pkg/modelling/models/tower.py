@@ -18,7 +18,11 @@ step is a single tt_dense_* launch.  Every GEMM is libtt's, on bf16x3 MFMA
   * forward_acts_pair / backward_acts_pair: the same per-layer work of the
     query and the candidate tower as ONE launch per layer and kind
     (tt_mlp_rows_pair, tt_mlp_wgrad_pair) on one stream, bit-identical to the
-    single calls.
+    single calls;
+  * optional (normalize=True, off by default; not in the reference): the
+    output rows L2-normalised and multiplied by output_scale (tt_l2norm_rows /
+    tt_l2norm_rows_grad) for cosine scoring — a dead, all-zero embedding stays
+    zero and gets no gradient.
 """
 from __future__ import annotations
 
@@ -39,6 +43,18 @@ __all__ = ["Tower", "DenseStack", "pair_compatible", "forward_acts_pair", "backw
 # (C3 step, 3 interleaved runs each: unfused 0.535-0.541 vs 0.533-0.536 ms;
 # fused apply 0.570-0.573 vs 0.564-0.565 ms — off)
 IGRAD_FIRST = os.environ.get("TT_IGRAD_FIRST", "0") == "1"
+
+
+def check_output_scale(normalize, output_scale) -> Tuple[bool, float]:
+    """(normalize, output_scale) of a tower's output, validated: the scale is
+    finite and is 1 unless the output is normalised."""
+    normalize, output_scale = bool(normalize), float(output_scale)
+    if output_scale != output_scale or output_scale in (float("inf"), float("-inf")):
+        raise ValueError(f"output_scale={output_scale} must be finite")
+    if output_scale != 1.0 and not normalize:
+        raise ValueError("output_scale != 1 needs normalize=True (on an un-normalised output it only rescales "
+                         "the top layer)")
+    return normalize, output_scale
 
 
 def _rows(p: dict) -> torch.Tensor:
@@ -72,13 +88,23 @@ class _DenseStackFn(torch.autograd.Function):
     def forward(ctx, x, flat, stack):
         acts = stack.forward_acts(x, flat)
         ctx.stack = stack
+        if stack.normalize:
+            (y, inv), = hip_ops.l2norm_rows([(acts[-1], stack.output_scale)])
+            ctx.save_for_backward(flat, inv, *acts)
+            return y
         ctx.save_for_backward(flat, *acts)
         return acts[-1]
 
     @staticmethod
     def backward(ctx, gout):
-        flat, *acts = ctx.saved_tensors
-        gx, gflat = ctx.stack.backward_acts(acts, flat, gout.contiguous(), None, ctx.needs_input_grad[0])
+        if ctx.stack.normalize:
+            flat, inv, *acts = ctx.saved_tensors
+            # the gradient with respect to the un-normalised top activation
+            (gout,) = hip_ops.l2norm_rows_grad([(acts[-1], inv, gout.contiguous(), ctx.stack.output_scale)])
+        else:
+            flat, *acts = ctx.saved_tensors
+            gout = gout.contiguous()
+        gx, gflat = ctx.stack.backward_acts(acts, flat, gout, None, ctx.needs_input_grad[0])
         return gx, gflat, None
 
 
@@ -92,14 +118,23 @@ class DenseStack:
     caller that builds a stack directly opts in to wider layers knowingly;
     Tower passes MAX_WIDTH = 4096, the kernels' own bound (tt_mlp_rows in
     column groups of <= 384, tt_mlp_wgrad's Ka, N <= 4096), so the public
-    API takes any width up to it.  There is no fallback GEMM above either."""
+    API takes any width up to it.  There is no fallback GEMM above either.
+
+    normalize (off by default): the stack's output is its top activation with
+    L2-normalised rows times output_scale (tt_l2norm_rows; a zero row stays
+    zero), for cosine scoring.  forward_acts / backward_acts are unaffected:
+    the stored activations keep the un-normalised top activation (the top
+    layer's ReLU mask), and whoever calls them normalises (this class's
+    __call__; the fused loss nodes in losses.py, which normalise both towers'
+    outputs in one launch).  output_scale != 1 needs normalize."""
 
     MAX_WIDTH = 4096  # tt_mlp_rows / tt_mlp_wgrad: N, Ka <= 4096
 
     def __init__(self, in_dim: int, units: List[int], device: torch.device, generator: torch.Generator, *,
-                 max_width: int = 384):
+                 max_width: int = 384, normalize: bool = False, output_scale: float = 1.0):
         if not 1 <= max_width <= self.MAX_WIDTH:
             raise ValueError(f"max_width={max_width} must be in 1..{self.MAX_WIDTH} (tt_mlp_rows, tt_mlp_wgrad)")
+        self.normalize, self.output_scale = check_output_scale(normalize, output_scale)
         self.layout: List[Tuple[int, int, int, int]] = []  # (w_off, fan_in, fan_out, b_off)
         off = 0
         fan_in = in_dim
@@ -339,7 +374,10 @@ class DenseStack:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and (x.requires_grad or self.flat.requires_grad):
             return _DenseStackFn.apply(x, self.flat, self)
-        return self.forward_acts(x, self.flat.detach())[-1]
+        out = self.forward_acts(x, self.flat.detach())[-1]
+        if self.normalize:
+            (out, _), = hip_ops.l2norm_rows([(out, self.output_scale)])
+        return out
 
 
 def pair_compatible(a: "DenseStack", b: "DenseStack") -> bool:
@@ -417,11 +455,19 @@ class Tower(AbstractKerasModel):
     The input width (the features' concatenated embeddings and numerics) and
     every layer's units may be up to 4096 (DenseStack.MAX_WIDTH); a wider
     layer raises ValueError.
+
+    normalize: bool
+        The tower's output rows are L2-normalised (cosine scoring; a dead,
+        all-zero embedding stays zero and gets no gradient).  Off by default.
+    output_scale: float
+        The normalised output is multiplied by it (TwoTowerModel gives the
+        query tower 1 / temperature).  Anything but 1 needs normalize.
     """
 
     def __init__(self, features: List[Feature], joint_embedding_size: int,
                  hidden_units: Optional[List[int]] = None, device: Optional[torch.device] = None,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, normalize: bool = False, output_scale: float = 1.0):
+        self.normalize, self.output_scale = check_output_scale(normalize, output_scale)
         self.features = features
         self.joint_embedding_size = joint_embedding_size
         self.hidden_units = hidden_units
@@ -436,7 +482,8 @@ class Tower(AbstractKerasModel):
         # the public API takes every width the kernels do (DenseStack: why the
         # bare constructor's default is lower)
         self.dense = DenseStack(self.input_layer.output_dim, units, self.device, self._generator,
-                                max_width=DenseStack.MAX_WIDTH)
+                                max_width=DenseStack.MAX_WIDTH, normalize=self.normalize,
+                                output_scale=self.output_scale)
         self.model_layers = [self.input_layer, self.dense]
 
     def call(self, x: Dict[str, torch.Tensor], training: bool = True) -> torch.Tensor:

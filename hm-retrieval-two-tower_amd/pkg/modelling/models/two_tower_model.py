@@ -8,6 +8,9 @@ train_step (two_tower_model.py:94-130) on MI355X:
   4. MLP backward                                 tt_mlp_wgrad weight + bias gradients and
                                                   tt_mlp_rows input gradients (ReluGrad fused)
   5. optimizer                                    tt_dense_adagrad + tt_sparse_adagrad (dedup in-kernel)
+With normalize_embeddings (opt-in cosine scoring, temperature in the query
+side's scale): tt_l2norm_rows on both towers' outputs before 3 and
+tt_l2norm_rows_grad on dQ, dC after it, one launch each.
 Every launch is stream-ordered with no host synchronisation, so the whole step
 can be captured once and replayed as a hipGraph (GraphedTrainStep).
 """
@@ -24,7 +27,8 @@ from pkg.schema.features import Feature
 from pkg.schema.schema import Schema
 from pkg.modelling.device import default_device, make_generator
 from pkg.modelling.layers.logq_correction import LogQCorrection
-from pkg.modelling.losses import TOWER_C_SCOPE, InBatchSoftmaxCrossEntropy, towers_inbatch_softmax_xent
+from pkg.modelling.losses import (TOWER_C_SCOPE, InBatchSoftmaxCrossEntropy, normalized_outputs,
+                                  towers_inbatch_softmax_xent)
 from pkg.modelling.models.abstract_keras_model import AbstractKerasModel, TensorSpec
 from pkg.modelling import hip_ops
 from pkg.modelling.layers.input_layer import InputLayer
@@ -79,6 +83,19 @@ class TwoTowerModel(AbstractKerasModel):
         out-of-vocabulary candidates, id 0, count as one) is no negative of
         that row, in training and in evaluation — a departure from the
         reference's loss (TensorFlow Recommenders' remove_accidental_hits).
+    normalize_embeddings: bool
+        Off (the default): scores are dot products of the towers' ReLU
+        outputs, the reference's.  On: both towers' outputs are L2-normalised
+        (a dead, all-zero embedding stays zero and gets no gradient), so a
+        score is a cosine in [0, 1] — two launches more per train step
+        (tt_l2norm_rows, tt_l2norm_rows_grad), the loss kernels unchanged.
+    temperature: Optional[float]
+        Softmax temperature T > 0 of the cosine scores (TensorFlow
+        Recommenders' Retrieval(temperature=...)); needs normalize_embeddings.
+        It is the query tower's output scale 1 / T, so call() returns the
+        training logits cos / T (before logQ), an index built from the
+        candidate tower and queried through the query tower returns cos / T,
+        and the ranking does not depend on T.  None: T = 1.
     """
 
     def __init__(self, query_features: List[Feature], candidate_features: List[Feature], candidate_id_col: str,
@@ -86,7 +103,17 @@ class TwoTowerModel(AbstractKerasModel):
                  candidate_tower_units: Optional[List[int]] = None,
                  candidate_prob_lookup: Optional[Dict[str, float]] = None,
                  device: Optional[torch.device] = None, seed: Optional[int] = None,
-                 fused_optimizer_apply: bool = False, remove_accidental_hits: bool = False):
+                 fused_optimizer_apply: bool = False, remove_accidental_hits: bool = False,
+                 normalize_embeddings: bool = False, temperature: Optional[float] = None):
+        self.normalize_embeddings = bool(normalize_embeddings)
+        if temperature is not None:
+            temperature = float(temperature)
+            if not 0.0 < temperature < float("inf"):
+                raise ValueError(f"temperature={temperature} must be a positive finite number")
+            if not self.normalize_embeddings:
+                raise ValueError("temperature needs normalize_embeddings=True (on unbounded dot products it only "
+                                 "rescales the top layers)")
+        self.temperature = temperature
         self.remove_accidental_hits = bool(remove_accidental_hits)
         # apply each tower's Adagrad step inside the backward (see train_step)
         self.fused_optimizer_apply = bool(fused_optimizer_apply)
@@ -97,8 +124,13 @@ class TwoTowerModel(AbstractKerasModel):
         self.candidate_id_col = candidate_id_col
         self.device = device if device is not None else default_device()
         gen = make_generator(seed)
-        self.query_tower = Tower(query_features, joint_embedding_size, query_tower_units, self.device, gen)
-        self.candidate_tower = Tower(candidate_features, joint_embedding_size, candidate_tower_units, self.device, gen)
+        # the temperature folds into the query side's normalisation scale:
+        # logits = (q / |q| / T) . (c / |c|), so no loss or index kernel changes
+        self.query_tower = Tower(query_features, joint_embedding_size, query_tower_units, self.device, gen,
+                                 normalize=self.normalize_embeddings,
+                                 output_scale=1.0 / temperature if temperature is not None else 1.0)
+        self.candidate_tower = Tower(candidate_features, joint_embedding_size, candidate_tower_units, self.device, gen,
+                                     normalize=self.normalize_embeddings)
         self.logq_correction = LogQCorrection(candidate_prob_lookup) if candidate_prob_lookup else None
         self._logq_rows: Optional[torch.Tensor] = None
         self.optimizer = None
@@ -213,7 +245,12 @@ class TwoTowerModel(AbstractKerasModel):
             return towers_inbatch_softmax_xent(qi, ci, self.query_tower.dense, self.candidate_tower.dense, logq,
                                                self.loss.reduction, getattr(self, "_on_tower", None),
                                                getattr(self, "_on_dx", None), ids)
-        return self.loss(self.query_tower.dense(qi), self.candidate_tower.dense(ci), logq, ids)
+        sq, sc = self.query_tower.dense, self.candidate_tower.dense
+        if sq.normalize or sc.normalize:  # both outputs normalised in one launch, after both towers
+            q, c, _ = normalized_outputs(sq, sc, sq.forward_acts(qi, sq.flat.detach())[-1],
+                                         sc.forward_acts(ci, sc.flat.detach())[-1])
+            return self.loss(q, c, logq, ids)
+        return self.loss(sq(qi), sc(ci), logq, ids)
 
     def compile(self, loss=None, optimizer=None, **kwargs) -> None:
         """Keras-style compile: the loss must be the in-batch softmax CE

@@ -790,6 +790,62 @@ typedef struct {
 size_t tt_mlp_wgrad_pair_workspace_size(const tt_mlp_wgrad_problem* p);
 int tt_mlp_wgrad_pair(const tt_mlp_wgrad_problem* p, void* workspace, size_t workspace_bytes, tt_stream_t stream);
 
+/* Cosine scoring: L2 normalisation of the rows of the towers' joint
+ * embeddings, and its gradient (TensorFlow Recommenders'
+ * Retrieval(temperature=...) on normalised tower outputs; the reference has
+ * no such option).  1 or 2 jobs (the two towers' operands) in ONE launch;
+ * stream-ordered, no workspace, no allocation, no synchronisation.
+ *
+ * Forward, per row i:  ss_i = sum_k x_ik^2 in fp32;  inv_i = 1 / sqrt(ss_i)
+ * if ss_i > 0, else 0;  y_i = x_i * (scale * inv_i).  inv [rows] is written
+ * and holds the UNSCALED reciprocal norm.
+ * Gradient, per row i:  u_i = x_i * inv_i;
+ *   dx_i = scale * inv_i * (dy_i - u_i (u_i . dy_i)).
+ * Zero rows: a row with ss_i == 0 gives y_i = 0, inv_i = 0 and dx_i = 0
+ * exactly (+0.0f in every element): a dead embedding gets no gradient, as
+ * through its ReLU.  There is no epsilon (and none of the 1 / epsilon
+ * gradient an epsilon brings).
+ * Shapes: dim in 1..4096; every leading dimension (in floats) >= dim; rows
+ * need not be 16-byte aligned (any dim, odd leading dimensions): 16-byte
+ * accesses are used only for an operand whose base is 16-byte aligned and
+ * whose leading dimension is a multiple of 4.  Columns dim..ld of an output
+ * are never written.
+ * Aliasing: dx == dy (in place) is allowed; a row is read completely before
+ * any of it is written.  No other overlap of an output with an operand.
+ * Determinism: the summation order over a row is fixed (by column index
+ * only), so a row's result depends only on that row, dim and scale: not on
+ * rows, on addresses or leading dimensions, on which job holds it or on the
+ * other job.  A two-job launch equals two one-job launches bit for bit.
+ * rows == 0: TT_OK for that job, no work (its pointers are not looked at).
+ * TT_ERR_BAD_ARG (with a message, checked on the host before any launch):
+ * NULL jobs or a NULL pointer of a job with rows, num_jobs outside 1..2, dim
+ * outside 1..4096, a leading dimension < dim, rows outside 0..2^31, or a
+ * scale that is not finite. */
+typedef struct {
+  const float* x;
+  int64_t ldx;
+  float* y;
+  int64_t ldy;
+  float* inv;
+  int64_t rows;
+  int32_t dim;
+  float scale;
+} tt_l2norm_job;
+int tt_l2norm_rows(const tt_l2norm_job* jobs, int32_t num_jobs, tt_stream_t stream);
+typedef struct {
+  const float* x;
+  int64_t ldx;
+  const float* inv;
+  const float* dy;
+  int64_t lddy;
+  float* dx;
+  int64_t lddx;
+  int64_t rows;
+  int32_t dim;
+  float scale;
+} tt_l2norm_grad_job;
+int tt_l2norm_rows_grad(const tt_l2norm_grad_job* jobs, int32_t num_jobs, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
