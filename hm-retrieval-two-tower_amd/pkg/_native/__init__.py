@@ -25,6 +25,10 @@ __all__ = [
     "MlpWgradProblem",
     "L2NormJob",
     "L2NormGradJob",
+    "BagJob",
+    "BagGradJob",
+    "MAX_BAG_JOBS",
+    "BAG_POOLINGS",
     "MAX_SEGMENTS",
     "MAX_SOURCES",
     "lib",
@@ -160,6 +164,45 @@ class L2NormGradJob(ctypes.Structure):
         ("rows", c_int64),
         ("dim", c_int32),
         ("scale", c_float),
+    ]
+
+
+MAX_BAG_JOBS = 8  # TT_BAG_MAX_JOBS
+BAG_POOLINGS = {"sum": 0, "mean": 1, "sqrtn": 2}  # TT_BAG_SUM / TT_BAG_MEAN / TT_BAG_SQRTN
+
+
+class BagJob(ctypes.Structure):
+    _fields_ = [
+        ("table", c_void_p),
+        ("num_rows", c_int64),
+        ("dim", c_int32),
+        ("L", c_int32),
+        ("ids", c_void_p),
+        ("ids_row_stride", c_int64),
+        ("ids_pos_stride", c_int64),
+        ("pooling", c_int32),
+        ("col_offset", c_int32),
+        ("out", c_void_p),
+        ("out_stride", c_int64),
+        ("scale_out", c_void_p),
+    ]
+
+
+class BagGradJob(ctypes.Structure):
+    _fields_ = [
+        ("num_rows", c_int64),
+        ("dim", c_int32),
+        ("L", c_int32),
+        ("ids", c_void_p),
+        ("ids_row_stride", c_int64),
+        ("ids_pos_stride", c_int64),
+        ("pooling", c_int32),
+        ("col_offset", c_int32),
+        ("dout", c_void_p),
+        ("dout_stride", c_int64),
+        ("scale", c_void_p),
+        ("ids_flat", c_void_p),
+        ("grad", c_void_p),
     ]
 
 
@@ -392,6 +435,8 @@ _PROTOS = {
          c_void_p]),
     "tt_l2norm_rows": (c_int32, [c_void_p, c_int32, c_void_p]),
     "tt_l2norm_rows_grad": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "tt_gather_bag": (c_int32, [POINTER(BagJob), c_int32, c_int64, c_void_p]),
+    "tt_bag_grad_expand": (c_int32, [POINTER(BagGradJob), c_int32, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

@@ -145,7 +145,8 @@ class DeviceDataset:
     The columns (int32 rows / float32 values, 1-D, equal length) are stored
     as one [C, N] matrix of 32-bit words, int columns first then float
     columns, each group in sorted key order (GraphedTrainStep's static batch
-    layout).  An epoch's order is epoch_order(...) — the same batches, in the
+    layout).  An [N, L] int column (a sequence feature's ids) is stored as L
+    consecutive word rows and handed back as the [B, L] transposed view.  An epoch's order is epoch_order(...) — the same batches, in the
     same order, as EncodedDataset with the same seed — uploaded once per
     epoch; a batch is one tt_batch_take launch reading the position from a
     device cursor, so TwoTowerModel.fit can replay take + train step as one
@@ -171,8 +172,12 @@ class DeviceDataset:
             raise ValueError(f"columns must be non-empty and of one length, got {lens}")
         self.num_rows = lens.pop()
         words, ikeys, fkeys = [], [], []
+        self.int_widths: Dict[str, int] = {}  # word rows of each [N, L] int column
         for k in sorted(columns):
-            v = np.asarray(columns[k]).reshape(-1)
+            v = np.asarray(columns[k])
+            if v.ndim == 2 and v.shape[1] > 1 and v.dtype.kind in "iu":
+                self.int_widths[k] = v.shape[1]
+            v = v.reshape(-1)
             if v.dtype.kind in "iu":
                 if v.size and (v.min() < -(1 << 31) or v.max() >= (1 << 31)):
                     raise ValueError(f"column {k} does not fit int32")
@@ -183,6 +188,9 @@ class DeviceDataset:
                 raise TypeError(f"column {k} has dtype {v.dtype}; DeviceDataset holds int32 / float32 columns")
         self.int_keys, self.float_keys = ikeys, fkeys
         for k in ikeys:
+            if k in self.int_widths:
+                words.extend(np.ascontiguousarray(np.asarray(columns[k]).T, dtype=np.int32))
+                continue
             words.append(np.ascontiguousarray(np.asarray(columns[k]).reshape(-1), dtype=np.int32))
         for k in fkeys:
             words.append(np.ascontiguousarray(np.asarray(columns[k]).reshape(-1), dtype=np.float32).view(np.int32))
@@ -210,7 +218,7 @@ class DeviceDataset:
         return self.int_keys + self.float_keys
 
     def _shared(self) -> dict:
-        names = ("device", "num_rows", "int_keys", "float_keys", "words", "_perm", "_perm_tag", "_order_pool",
+        names = ("device", "num_rows", "int_keys", "float_keys", "int_widths", "words", "_perm", "_perm_tag", "_order_pool",
                  "_order_futures", "cursor", "status")
         return {k: self.__dict__[k] for k in names}
 
@@ -270,15 +278,19 @@ class DeviceDataset:
         return fut.result() if fut is not None else self._make_order(epoch)
 
     def view(self, words: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Batch dict of [B] views over a [C, B] word buffer."""
-        out = {k: words[i] for i, k in enumerate(self.int_keys)}
-        out.update({k: words[len(self.int_keys) + j].view(torch.float32) for j, k in enumerate(self.float_keys)})
+        """Batch dict of [B] views ([B, L] for an [N, L] column) over a [C, B] word buffer."""
+        out, row = {}, 0
+        for k in self.int_keys:
+            w = self.int_widths.get(k)
+            out[k] = words[row] if w is None else words[row:row + w].t()
+            row += w or 1
+        out.update({k: words[row + j].view(torch.float32) for j, k in enumerate(self.float_keys)})
         return out
 
     def take(self, rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The next `rows` examples as a [C, rows] word buffer (advances the cursor)."""
         if out is None:
-            out = torch.empty(len(self.keys), rows, dtype=torch.int32, device=self.device)
+            out = torch.empty(self.words.shape[0], rows, dtype=torch.int32, device=self.device)
         return hip_ops.batch_take(self.words, self._perm, self.cursor, out, True, self.status)
 
     def check_status(self) -> None:

@@ -916,6 +916,10 @@ class ShardedTrainStep:
         the N > 1 step's graph over RCCL (tests)."""
         from pkg.modelling.optimizer_factory import Adagrad
 
+        for f in list(model.query_features) + list(model.candidate_features):
+            if getattr(f, "is_sequence", False):
+                raise NotImplementedError(f"ShardedTrainStep does not support sequence features (feature {f.name!r}, "
+                                          f"sequence_length={f.sequence_length})")
         opt = model.optimizer
         if not isinstance(opt, Adagrad):
             raise NotImplementedError("ShardedTrainStep supports the Adagrad optimizer")

@@ -40,7 +40,9 @@ FORMAT = "hm-two-tower-amd/1"
 # ---- features -------------------------------------------------------------
 def _feature_spec(f: Feature) -> dict:
     return {"name": f.name, "dtype": f.dtype.name, "family": f.feature_family.value,
-            "embedding_size": f.embedding_size, "max_vocab_size": f.max_vocab_size}
+            "embedding_size": f.embedding_size, "max_vocab_size": f.max_vocab_size,
+            # sequence features (files written before these fields load as None, "mean")
+            "sequence_length": f.sequence_length, "pooling": f.pooling}
 
 
 def _vocab_arrays(features: Sequence[Feature], prefix: str) -> Dict[str, np.ndarray]:
@@ -57,7 +59,8 @@ def _features_from(specs: List[dict], arrays, prefix: str) -> List[Feature]:
         key = f"{prefix}vocab.{s['name']}"
         vocab = [str(v) for v in arrays[key].tolist()] if key in arrays else None
         feats.append(Feature(s["name"], dtypes.as_dtype(s["dtype"]), FeatureFamily(s["family"]),
-                             embedding_size=s["embedding_size"], vocab=vocab, max_vocab_size=s["max_vocab_size"]))
+                             embedding_size=s["embedding_size"], vocab=vocab, max_vocab_size=s["max_vocab_size"],
+                             sequence_length=s.get("sequence_length"), pooling=s.get("pooling", "mean")))
     return feats
 
 

@@ -36,6 +36,8 @@ __all__ = [
     "inbatch_prep",
     "l2norm_rows",
     "l2norm_rows_grad",
+    "gather_bag",
+    "bag_grad_expand",
     "probe_arm",
     "probe_arm_repeat",
     "route_requests",
@@ -485,13 +487,13 @@ def sparse_sort(tables: Sequence[dict], batch: int, ws_tag: str = "sparse", slot
 
 
 def sparse_adam(tables: Sequence[dict], batch: int, grad: torch.Tensor, lr: float, beta1: float, beta2: float,
-                epsilon: float, step: int) -> None:
+                epsilon: float, step: int, ws_tag: str = "sparse") -> None:
     _req(grad, "grad", torch.float32, 2)
     ld = _row_major(grad, "grad")
     arr = _sparse_tables(tables, batch, adam=True)
     L = lib()
     need = L.tt_sparse_workspace_size(arr, len(tables), batch)
-    ws = Workspace.get(need, grad.device, "sparse")
+    ws = Workspace.get(need, grad.device, ws_tag)
     check(L.tt_sparse_adam(arr, len(tables), batch, grad.data_ptr(), ld, lr, beta1, beta2, epsilon, step,
                            ws.data_ptr(), ws.numel(), _stream()))
 
@@ -1479,3 +1481,93 @@ def l2norm_rows_grad(jobs: Sequence[tuple]) -> List[torch.Tensor]:
         out.append(dx)
     check(lib().tt_l2norm_rows_grad(arr, len(jobs), _stream()))
     return out
+
+
+# --------------------------------------------------------------------------
+# Sequence features: pooled embedding bags and their gradient expansion
+# --------------------------------------------------------------------------
+def _bag_ids(ids: torch.Tensor, name: str, batch: int, like: torch.Tensor) -> Tuple[int, int, int]:
+    """ids [batch, L] int32 with any (non-negative) strides -> (L, row stride, slot stride)."""
+    _req(ids, name, torch.int32, 2)
+    if ids.shape[0] != batch or ids.device != like.device:
+        raise ValueError(f"{name} must be [{batch}, L] int32 on {like.device}, got {tuple(ids.shape)} on {ids.device}")
+    if ids.stride(0) < 0 or ids.stride(1) < 0:
+        raise ValueError(f"{name}: negative strides are not supported")
+    return ids.shape[1], ids.stride(0), ids.stride(1)
+
+
+def _bag_pooling(pooling: str) -> int:
+    if pooling not in _native.BAG_POOLINGS:
+        raise ValueError(f"pooling must be one of {sorted(_native.BAG_POOLINGS)}, got {pooling!r}")
+    return _native.BAG_POOLINGS[pooling]
+
+
+def _bag_scale(t: torch.Tensor, name: str, batch: int, like: torch.Tensor) -> None:
+    _req(t, name, torch.float32, 1)
+    if t.numel() != batch or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{name} must be a contiguous [{batch}] float32 tensor on {like.device}")
+
+
+def gather_bag(jobs: Sequence[tuple], batch: int) -> None:
+    """Pooled embedding bags of 1..8 sequence features in ONE launch
+    (tt_gather_bag).  Each job is (table [V, D], ids [batch, L] int32 with any
+    strides, pooling "sum" | "mean" | "sqrtn", out [batch, >= col_offset + D]
+    fp32 with unit column stride, col_offset, scale_out [batch]): columns
+    [col_offset, col_offset + D) of out receive the pooled rows of the valid
+    slots (0 <= id < V; -1 pads), scale_out the factor applied (0 for an empty
+    bag).  The other columns of out are not touched."""
+    if not 1 <= len(jobs) <= _native.MAX_BAG_JOBS:
+        raise ValueError(f"gather_bag takes 1..{_native.MAX_BAG_JOBS} jobs")
+    arr = (_native.BagJob * len(jobs))()
+    for i, (table, ids, pooling, out, off, scale_out) in enumerate(jobs):
+        _req(table, f"table[{i}]", torch.float32, 2)
+        if not table.is_contiguous():
+            raise ValueError(f"table[{i}] must be contiguous")
+        L, rs, ps = _bag_ids(ids, f"ids[{i}]", batch, table)
+        _req(out, f"out[{i}]", torch.float32, 2)
+        if out.shape[0] != batch or out.device != table.device:
+            raise ValueError(f"out[{i}] must have {batch} rows on {table.device}")
+        ld = _norm_ld(out, f"out[{i}]")
+        if off < 0 or off + table.shape[1] > max(out.shape[1], 1):
+            raise ValueError(f"out[{i}]: columns [{off}, {off + table.shape[1]}) outside its {out.shape[1]} columns")
+        _bag_scale(scale_out, f"scale_out[{i}]", batch, table)
+        q = arr[i]
+        q.table, q.num_rows, q.dim, q.L = table.data_ptr(), table.shape[0], table.shape[1], L
+        q.ids, q.ids_row_stride, q.ids_pos_stride = ids.data_ptr(), rs, ps
+        q.pooling, q.col_offset = _bag_pooling(pooling), off
+        q.out, q.out_stride, q.scale_out = out.data_ptr(), ld, scale_out.data_ptr()
+    check(lib().tt_gather_bag(arr, len(jobs), batch, _stream()))
+
+
+def bag_grad_expand(jobs: Sequence[tuple], batch: int) -> None:
+    """The flat sparse problem of 1..8 bag features in ONE launch
+    (tt_bag_grad_expand).  Each job is (num_rows, ids [batch, L], pooling,
+    dout [batch, *], col_offset, scale [batch] from gather_bag, ids_flat
+    [batch * L] int32, grad [batch * L, D] fp32 contiguous): ids_flat[b * L +
+    l] is the slot's id or -1, and the grad row of every valid slot is
+    dout[b, col_offset : col_offset + D] * scale[b].  Rows of invalid slots
+    are not written."""
+    if not 1 <= len(jobs) <= _native.MAX_BAG_JOBS:
+        raise ValueError(f"bag_grad_expand takes 1..{_native.MAX_BAG_JOBS} jobs")
+    arr = (_native.BagGradJob * len(jobs))()
+    for i, (num_rows, ids, pooling, dout, off, scale, ids_flat, grad) in enumerate(jobs):
+        _req(dout, f"dout[{i}]", torch.float32, 2)
+        L, rs, ps = _bag_ids(ids, f"ids[{i}]", batch, dout)
+        _req(grad, f"grad[{i}]", torch.float32, 2)
+        dim = grad.shape[1]
+        if grad.shape[0] != batch * L or not grad.is_contiguous() or grad.device != dout.device:
+            raise ValueError(f"grad[{i}] must be a contiguous [{batch * L}, D] float32 tensor on {dout.device}")
+        _req(ids_flat, f"ids_flat[{i}]", torch.int32, 1)
+        if ids_flat.numel() != batch * L or not ids_flat.is_contiguous() or ids_flat.device != dout.device:
+            raise ValueError(f"ids_flat[{i}] must be a contiguous [{batch * L}] int32 tensor on {dout.device}")
+        if dout.shape[0] != batch or off < 0 or off + dim > dout.shape[1]:
+            raise ValueError(f"dout[{i}] must be [{batch}, >= {off + dim}], got {tuple(dout.shape)}")
+        ld = _norm_ld(dout, f"dout[{i}]")
+        _bag_scale(scale, f"scale[{i}]", batch, dout)
+        q = arr[i]
+        q.num_rows, q.dim, q.L = int(num_rows), dim, L
+        q.ids, q.ids_row_stride, q.ids_pos_stride = ids.data_ptr(), rs, ps
+        q.pooling, q.col_offset = _bag_pooling(pooling), off
+        q.dout, q.dout_stride, q.scale = dout.data_ptr(), ld, scale.data_ptr()
+        q.ids_flat, q.grad = ids_flat.data_ptr(), grad.data_ptr()
+    check(lib().tt_bag_grad_expand(arr, len(jobs), batch, _stream()))

@@ -7,6 +7,11 @@ encoded (Feature.encode); on the device a batch is a dict of int32 row ids
 (input_layer.py:37-41, 66-68) is ONE libtt launch (tt_gather_grouped) that
 writes every feature's rows into its column range of the output.
 
+A sequence feature (Feature(sequence_length=L)) arrives as int32 [B, L] ids
+(-1 pads) and owns embedding_size columns like any categorical feature: its
+pooled bag is written into them by ONE further launch (tt_gather_bag) for all
+such features of all layers in the call; without one nothing is launched.
+
 The backward pass of the gather does not build dense table gradients: it
 keeps the gradient w.r.t. the concatenated output (the reference's
 IndexedSlices values) and the ids, and the optimizer applies the sparse
@@ -43,11 +48,23 @@ class EmbeddingTable:
         return f"EmbeddingTable({self.name!r}, rows={self.num_rows}, dim={self.dim})"
 
 
+def _gather_bags(layers, outs, batch: int) -> None:
+    """The pooled bags of every sequence feature of `layers`, written into
+    their column ranges of `outs` after the gather: one tt_gather_bag launch
+    per 8 jobs, none without a sequence feature."""
+    jobs = [(bag["table"].weight, bag["ids"], bag["pooling"], out, bag["grad_col_offset"], bag["scale"])
+            for layer, out in zip(layers, outs) for bag in layer._last_bags]
+    for i in range(0, len(jobs), hip_ops._native.MAX_BAG_JOBS):
+        hip_ops.gather_bag(jobs[i:i + hip_ops._native.MAX_BAG_JOBS], batch)
+
+
 class _GatherFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, layer, segments, batch):
         out = torch.empty(batch, layer.row_stride, dtype=torch.float32, device=layer.device)
-        hip_ops.gather_grouped(segments, batch, out)
+        if segments:
+            hip_ops.gather_grouped(segments, batch, out)
+        _gather_bags([layer], [out], batch)
         ctx.layer = layer
         return out[:, : layer.output_dim]
 
@@ -66,7 +83,12 @@ class _MultiGatherFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layers, seglists, batch, extra, pack_jobs, *anchors):
         outs = [torch.empty(batch, l.row_stride, dtype=torch.float32, device=l.device) for l in layers]
-        hip_ops.gather_multi(list(zip(seglists, outs)) + list(extra), batch, pack_jobs=pack_jobs)
+        calls = [(segs, out) for segs, out in zip(seglists, outs) if segs] + list(extra)
+        if calls:
+            hip_ops.gather_multi(calls, batch, pack_jobs=pack_jobs)
+        elif pack_jobs:
+            hip_ops.mlp_pack_many(pack_jobs)
+        _gather_bags(layers, outs, batch)
         ctx.layers = layers
         return tuple(o[:, : l.output_dim] for o, l in zip(outs, layers))
 
@@ -103,6 +125,8 @@ class InputLayer:
         self.row_stride = (self.output_dim + 3) // 4 * 4
         self._anchor = torch.zeros((), requires_grad=True)
         self.last_ids: Dict[str, torch.Tensor] = {}
+        self._last_calls: List[tuple] = []
+        self._last_bags: List[dict] = []
         self.last_grad: Optional[torch.Tensor] = None
 
     def _init_embedding_layers(self) -> None:
@@ -156,6 +180,20 @@ class InputLayer:
             t = t.to(self.device)
         return t.contiguous()
 
+    def _bag_ids(self, v, feature: Feature) -> torch.Tensor:
+        """A sequence feature's batch as int32 [B, L] on the device, its strides
+        kept (the kernel reads any); raw nested values go through encode."""
+        if not isinstance(v, torch.Tensor):
+            if not (isinstance(v, np.ndarray) and v.dtype.kind in "iu"):
+                v = feature.encode(v)
+            v = torch.as_tensor(v)
+        if v.dim() != 2 or v.shape[1] != feature.sequence_length:
+            raise ValueError(f"sequence feature {feature.name} takes [B, {feature.sequence_length}] ids, "
+                             f"got shape {tuple(v.shape)}")
+        if v.dtype != torch.int32:
+            v = v.to(torch.int32)
+        return v if v.device == self.device else v.to(self.device)
+
     def _segments(self, x: Dict[str, torch.Tensor]):
         segments = []
         batch = None
@@ -166,7 +204,17 @@ class InputLayer:
             batch = v.numel() if batch is None else batch
             segments.append((v, None, len(segments)))
         ids_by_call = []
+        bags = []
         for f, off in zip(self.categorical_features, self.column_offsets()):
+            if f.is_sequence:  # its column range is left to a bag job
+                ids = self._bag_ids(x[f.name], f)
+                batch = ids.shape[0] if batch is None else batch
+                if ids.shape[0] != batch:
+                    raise ValueError(f"feature {f.name} has {ids.shape[0]} rows, expected {batch}")
+                bags.append(dict(table=self.embedding_layers[f.name], ids=ids, grad_col_offset=off,
+                                 pooling=f.pooling,
+                                 scale=torch.empty(batch, dtype=torch.float32, device=self.device)))
+                continue
             ids = self._ids(x[f.name], f)
             batch = ids.numel() if batch is None else batch
             if ids.numel() != batch:
@@ -176,11 +224,13 @@ class InputLayer:
         if batch is None:
             raise ValueError("InputLayer called with no features")
         self._last_calls = ids_by_call
+        self._last_bags = bags
         self.last_grad = None
         return segments, batch
 
     def __call__(self, x: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """Pass a dict of [B] or [B,1] tensors; returns [B, output_dim] fp32."""
+        """Pass a dict of [B] or [B,1] tensors ([B, L] for a sequence feature);
+        returns [B, output_dim] fp32."""
         segments, batch = self._segments(x)
         return _GatherFn.apply(self._anchor, self, segments, batch)
 
@@ -207,8 +257,14 @@ class InputLayer:
         return list(_MultiGatherFn.apply(list(layers), [segs for segs, _ in prepared], batches.pop(), list(extra),
                                          pack_jobs or None, *[l._anchor for l in layers]))
 
+    def bag_sources(self) -> List[dict]:
+        """Per sequence feature of the last call: table, ids [B, L], pooling,
+        the grad column of its segment and the scale the forward applied."""
+        return list(self._last_bags)
+
     def sparse_sources(self) -> List[dict]:
-        """Per table: its lookups of the last call as (ids, grad column) sources."""
+        """Per table: its one-id lookups of the last call as (ids, grad column)
+        sources (sequence features: bag_sources)."""
         by_name: Dict[str, dict] = {}
         for name, ids, off in self._last_calls:
             d = by_name.setdefault(name, {"table": self.embedding_layers[name], "ids": [], "grad_col_offset": []})

@@ -497,7 +497,8 @@ class Tower(AbstractKerasModel):
             return self.call(x, training)
 
     def get_input_signature(self) -> Dict[str, TensorSpec]:
-        return {f.name: TensorSpec((None, 1), f.dtype, f.name) for f in self.features}
+        return {f.name: TensorSpec((None, f.sequence_length if f.is_sequence else 1), f.dtype, f.name)
+                for f in self.features}
 
     # -- parameters --------------------------------------------------------
     def dense_parameters(self) -> List[torch.Tensor]:

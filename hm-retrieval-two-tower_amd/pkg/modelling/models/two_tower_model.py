@@ -121,6 +121,8 @@ class TwoTowerModel(AbstractKerasModel):
         self.candidate_features = candidate_features
         if candidate_id_col not in [f.name for f in candidate_features]:
             raise ValueError(f"candidate_id_col {candidate_id_col} not a candidate feature")
+        if any(f.name == candidate_id_col and f.is_sequence for f in candidate_features):
+            raise ValueError(f"candidate_id_col {candidate_id_col} may not be a sequence feature")
         self.candidate_id_col = candidate_id_col
         self.device = device if device is not None else default_device()
         gen = make_generator(seed)
@@ -450,7 +452,8 @@ class TwoTowerModel(AbstractKerasModel):
         )
 
     def get_input_signature(self) -> Dict[str, TensorSpec]:
-        return {f.name: TensorSpec((None, 1), f.dtype, f.name) for f in self.candidate_features + self.query_features}
+        return {f.name: TensorSpec((None, f.sequence_length if f.is_sequence else 1), f.dtype, f.name)
+                for f in self.candidate_features + self.query_features}
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         sd = {f"query_tower.{k}": v for k, v in self.query_tower.state_dict().items()}
@@ -483,7 +486,9 @@ class GraphedTrainStep:
     """Capture TwoTowerModel.train_step once as a hipGraph and replay it.
 
     The batch lives in two static device buffers (int32 ids [K, B], float32
-    values [F, B]); a replay is one D2D copy per buffer (or none, for
+    values [F, B]; a sequence feature's [B, L] ids take L consecutive int rows
+    and are read through the transposed view of those rows, so no copy is made
+    inside the graph); a replay is one D2D copy per buffer (or none, for
     `replay()`), then the whole step — gathers, MLP GEMMs, the fused
     loss kernels and the optimizer kernels — with no Python or launch
     overhead.  Warm-up steps (run eagerly on a side stream before capture)
@@ -506,22 +511,29 @@ class GraphedTrainStep:
             if not source.batch_size:
                 raise ValueError("a graphed DeviceDataset source needs a batch_size")
             self.int_keys, self.float_keys = list(source.int_keys), list(source.float_keys)
+            self.int_widths = dict(source.int_widths)
             self.batch_size = int(source.batch_size)
             ex = None
         else:
-            ex = {k: self._to_dev(v, model.device).reshape(-1) for k, v in example_batch.items()}
+            ex = {k: self._flat(self._to_dev(v, model.device)) for k, v in example_batch.items()}
             self.int_keys = sorted(k for k, v in ex.items() if v.dtype != torch.float32)
             self.float_keys = sorted(k for k, v in ex.items() if v.dtype == torch.float32)
+            # word rows per int key: L for a [B, L] column, none recorded for [B]
+            self.int_widths = {k: ex[k].shape[1] for k in self.int_keys if ex[k].dim() == 2}
             self.batch_size = next(iter(ex.values())).shape[0]
         B = self.batch_size
-        K, F = len(self.int_keys), len(self.float_keys)
+        K, F = len(self.int_keys) + sum(w - 1 for w in self.int_widths.values()), len(self.float_keys)
         # one [K + F, B] buffer of 32-bit words: int rows first, then float rows
         # (the DeviceDataset layout, so one take launch fills the whole batch)
         self._wbuf = torch.empty(max(K + F, 1), B, dtype=torch.int32, device=model.device)
         self._ibuf = self._wbuf[:K] if K else torch.empty(1, B, dtype=torch.int32, device=model.device)
         self._fbuf = (self._wbuf[K:K + F].view(torch.float32) if F
                       else torch.empty(1, B, dtype=torch.float32, device=model.device))
-        self.static = {k: self._ibuf[i] for i, k in enumerate(self.int_keys)}
+        self.static, row = {}, 0
+        for k in self.int_keys:
+            w = self.int_widths.get(k)
+            self.static[k] = self._ibuf[row] if w is None else self._ibuf[row:row + w].t()
+            row += w or 1
         self.static.update({k: self._fbuf[i] for i, k in enumerate(self.float_keys)})
         self.loss_total = torch.zeros((), dtype=torch.float64, device=model.device)
         if ex is not None:
@@ -565,17 +577,30 @@ class GraphedTrainStep:
         t = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
         return t.to(device)
 
+    @staticmethod
+    def _flat(t: torch.Tensor) -> torch.Tensor:
+        """[B] for a one-value column ([B] or [B, 1]); an int [B, L > 1] column keeps its axis."""
+        if t.dim() == 2 and t.shape[1] > 1 and t.dtype != torch.float32:
+            return t
+        return t.reshape(-1)
+
+    def _int_rows(self, k: str, t: torch.Tensor) -> torch.Tensor:
+        """Key k's batch as its [rows, B] block of the int buffer."""
+        w = self.int_widths.get(k)
+        t = t.to(torch.int32)
+        return t.reshape(1, -1) if w is None else t.reshape(-1, w).t()
+
     def pack(self, batch: Dict[str, Any]):
         """Device buffers laid out like the static batch (copy with one D2D each)."""
-        ib = torch.stack([self._to_dev(batch[k], self.model.device).reshape(-1).to(torch.int32)
-                          for k in self.int_keys]) if self.int_keys else self._ibuf.clone()
+        ib = torch.cat([self._int_rows(k, self._to_dev(batch[k], self.model.device))
+                        for k in self.int_keys]) if self.int_keys else self._ibuf.clone()
         fb = torch.stack([self._to_dev(batch[k], self.model.device).reshape(-1).to(torch.float32)
                           for k in self.float_keys]) if self.float_keys else self._fbuf.clone()
         return ib.contiguous(), fb.contiguous()
 
     def load(self, batch: Dict[str, Any]) -> None:
         for k, v in batch.items():
-            self.static[k].copy_(self._to_dev(v, self.model.device).reshape(-1), non_blocking=True)
+            self.static[k].copy_(self._to_dev(v, self.model.device).reshape(self.static[k].shape), non_blocking=True)
 
     def replay(self) -> Dict[str, torch.Tensor]:
         self.graph.replay()

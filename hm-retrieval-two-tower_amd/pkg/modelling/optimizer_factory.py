@@ -55,6 +55,40 @@ class _Optimizer:
 
     minimize = apply_gradients
 
+    # -- sequence features: a tower's bag tables as flat sparse problems -------
+    BAG_WS_TAG = "sparse_bag"  # the regular tables' presorted keys may sit in "sparse"
+
+    def _apply_bags(self, tower, grad: Optional[torch.Tensor], apply) -> None:
+        """Expand the tower's input gradient into one gradient row per lookup of
+        its sequence features (ONE tt_bag_grad_expand launch per 8 features) and
+        hand every group of equal L to `apply(specs, batch * L, G)` as a flat
+        problem: one source per table, ids_flat, grad_ld = dim, column 0.  On
+        the current stream and workspace scope, after the tower's regular
+        sparse call; nothing is launched without a sequence feature."""
+        bags = tower.input_layer.bag_sources()
+        if not bags or grad is None:
+            return
+        if grad.stride(1) != 1:
+            grad = grad.contiguous()
+        B = grad.shape[0]
+        sizes = [(B * b["ids"].shape[1], b["table"].dim) for b in bags]
+        offs, total = [], 0
+        for n, dim in sizes:  # 256-byte aligned carves: ids_flat then G per feature
+            offs.append((total, total + (n * 4 + 255) // 256 * 256))
+            total = offs[-1][1] + (n * dim * 4 + 255) // 256 * 256
+        buf = hip_ops.Workspace.get(total, grad.device, "bag_grad")
+        jobs, by_len = [], {}
+        for b, (n, dim), (o_ids, o_g) in zip(bags, sizes, offs):
+            ids_flat = buf[o_ids:o_ids + n * 4].view(torch.int32)
+            G = buf[o_g:o_g + n * dim * 4].view(torch.float32).view(n, dim)
+            t = b["table"]
+            jobs.append((t.num_rows, b["ids"], b["pooling"], grad, b["grad_col_offset"], b["scale"], ids_flat, G))
+            by_len.setdefault(b["ids"].shape[1], []).append((t, ids_flat, G))
+        for i in range(0, len(jobs), hip_ops._native.MAX_BAG_JOBS):
+            hip_ops.bag_grad_expand(jobs[i:i + hip_ops._native.MAX_BAG_JOBS], B)
+        for L, group in by_len.items():  # tables of different L take separate calls
+            apply(group, B * L)
+
 
 class Adagrad(_Optimizer):
     def __init__(self, learning_rate: float = 0.001, initial_accumulator_value: float = 0.1, epsilon: float = 1e-7,
@@ -126,9 +160,21 @@ class Adagrad(_Optimizer):
         self.apply_dense(tower, flat_grad)
         self.apply_tower_sparse(tower, input_grad)
 
+    def _apply_bag_group(self, group, batch: int) -> None:
+        specs = []
+        for t, ids_flat, G in group:
+            (acc,) = self._slot(t.weight, 1, self.initial_accumulator_value)
+            specs.append(dict(table=t.weight, slot0=acc, ids=[ids_flat], grad_col_offset=[0], grad=G))
+        hip_ops.sparse_adagrad(specs, batch, None, self.learning_rate, self.epsilon, ws_tag=self.BAG_WS_TAG)
+
     def apply_tower_sparse(self, tower, input_grad: Optional[torch.Tensor]) -> None:
         """Tower's tables' sparse Adagrad step alone (apply_tower's second
-        half), on the current stream and workspace scope."""
+        half), on the current stream and workspace scope; its sequence
+        features' tables follow the regular call."""
+        self._apply_tower_tables(tower, input_grad)
+        self._apply_bags(tower, input_grad, self._apply_bag_group)
+
+    def _apply_tower_tables(self, tower, input_grad: Optional[torch.Tensor]) -> None:
         lr, eps = self.learning_rate, self.epsilon
         prep = getattr(self, "_tower_prep", {}).pop(id(tower), None)
         if input_grad is None:
@@ -197,6 +243,8 @@ class Adagrad(_Optimizer):
             else:
                 raise RuntimeError(f"apply_gradients: presorted state {prepared[0]}/{prepared[1]} does not match "
                                    f"this apply ({[id(s['table']) for s in specs]}/{batch})")
+        for tower in towers:
+            self._apply_bags(tower, tower.input_layer.last_grad, self._apply_bag_group)
 
     def check_status(self, device: Optional[torch.device] = None) -> None:
         """Raise if any sparse apply since the last check found keys that were
@@ -209,6 +257,7 @@ class Adagrad(_Optimizer):
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         for scope in ("", TOWER_C_SCOPE):
             hip_ops.sparse_status(dev, "sparse", scope)
+            hip_ops.sparse_status(dev, self.BAG_WS_TAG, scope)
 
 
 class Adam(_Optimizer):
@@ -236,7 +285,18 @@ class Adam(_Optimizer):
                 m, v = self._slot(t.weight, 2, 0.0)
                 specs.append(dict(table=t.weight, slot0=m, slot1=v, ids=src["ids"],
                                   grad_col_offset=src["grad_col_offset"]))
-            hip_ops.sparse_adam(specs, layer.last_grad.shape[0], layer.last_grad, lr, b1, b2, eps, step)
+            if specs:
+                hip_ops.sparse_adam(specs, layer.last_grad.shape[0], layer.last_grad, lr, b1, b2, eps, step)
+
+            def apply_group(group, batch):
+                bag_specs = []
+                for t, ids_flat, G in group:
+                    m, v = self._slot(t.weight, 2, 0.0)
+                    bag_specs.append(dict(table=t.weight, slot0=m, slot1=v, ids=[ids_flat], grad_col_offset=[0],
+                                          grad=G))
+                hip_ops.sparse_adam(bag_specs, batch, group[0][2], lr, b1, b2, eps, step, ws_tag=self.BAG_WS_TAG)
+
+            self._apply_bags(tower, layer.last_grad, apply_group)
 
 
 class OptimizerFactory:

@@ -42,12 +42,23 @@ class Feature:
         values map to the OOV row 0.
     max_vocab_size: Optional[int]
         Max size of a vocab built from data (ignored if vocab is given).
+    sequence_length: Optional[int]
+        L >= 1 makes this a sequence feature: each example carries up to L
+        values (its last L are kept), embedded and pooled into one
+        embedding_size-wide segment (Keras Embedding + masked pooling).  Only
+        for ``pkg.dtypes.string`` with an embedding_size.
+    pooling: str
+        "mean", "sum" or "sqrtn": how a sequence feature's valid slots are
+        combined (TF safe_embedding_lookup_sparse's combiner).
 
     The id -> row mapping is the reference's StringLookup(num_oov_indices=1)
     (input_layer.py:33-36): vocab[i] -> row i+1, anything else -> row 0.
     """
 
     VALID_DTYPES = [dtypes.string, dtypes.float32]
+    VALID_POOLINGS = ["mean", "sum", "sqrtn"]
+    MAX_SEQUENCE_LENGTH = 1024  # tt_gather_bag's slot limit
+    PAD_ID = -1                 # the padding id of a sequence feature's slots
 
     def __init__(
         self,
@@ -57,6 +68,8 @@ class Feature:
         embedding_size: Optional[int] = None,
         vocab: Optional[List[str]] = None,
         max_vocab_size: Optional[int] = None,
+        sequence_length: Optional[int] = None,
+        pooling: str = "mean",
     ):
         self.name = name
         try:
@@ -87,6 +100,24 @@ class Feature:
                 raise TypeError(f"max_vocab_size must be an int, got {max_vocab_size}")
         self.max_vocab_size = max_vocab_size
 
+        if sequence_length is not None:
+            if isinstance(sequence_length, bool) or not isinstance(sequence_length, int):
+                raise TypeError(f"sequence_length must be an int, got {sequence_length}")
+            if not 1 <= sequence_length <= self.MAX_SEQUENCE_LENGTH:
+                raise ValueError(f"sequence_length must be in 1..{self.MAX_SEQUENCE_LENGTH}, got {sequence_length}")
+            if dtype != dtypes.string:
+                raise TypeError(f"Got sequence_length, dtype must be tf.string got {dtype}")
+            if not embedding_size:
+                raise ValueError(f"sequence feature {name} needs an embedding_size")
+        if pooling not in self.VALID_POOLINGS:
+            raise ValueError(f"pooling {pooling} not valid. Must be one of {self.VALID_POOLINGS}")
+        self.sequence_length = sequence_length
+        self.pooling = pooling
+
+    @property
+    def is_sequence(self) -> bool:
+        return self.sequence_length is not None
+
     def _init_vocab(self, vocab: Optional[List[str]] = None) -> None:
         """Check the dtype and init the vocab (features.py:83-104)."""
         if self.dtype != dtypes.string:
@@ -112,7 +143,10 @@ class Feature:
         """
         if self.name not in df.columns:
             raise ValueError(f"Feature name {self.name} not found in df cols {df.columns}")
-        v_counts = df[self.name].value_counts()
+        col = df[self.name]
+        if self.is_sequence:  # count the elements of the per-example sequences
+            col = pd.Series([v for seq in col for v in self._elements(seq)], dtype=object)
+        v_counts = col.value_counts()
         if self.max_vocab_size:
             vocab = list(v_counts.head(self.max_vocab_size).index)
         else:
@@ -147,7 +181,41 @@ class Feature:
             from pkg.schema.vocab import NativeVocab
 
             self._native = NativeVocab(self.vocab)
+        if self.is_sequence:
+            return self._encode_sequences(values, num_threads)
         return self._native.encode(values, num_threads)
+
+    @staticmethod
+    def _elements(seq) -> list:
+        """One example's values as a list; None / NaN / empty -> []."""
+        if seq is None:
+            return []
+        if isinstance(seq, (list, tuple)):
+            return list(seq)
+        if isinstance(seq, np.ndarray):
+            return seq.reshape(-1).tolist() if seq.ndim else Feature._elements(seq.item())
+        if isinstance(seq, (float, np.floating)) and np.isnan(seq):
+            return []
+        raise TypeError(f"a sequence feature takes a list, tuple or array per example, got {type(seq).__name__}")
+
+    def _encode_sequences(self, values: Sequence, num_threads: int = 0) -> np.ndarray:
+        """One sequence per example -> int32 [n, L]: the last L values of each,
+        in order, left-aligned and padded with PAD_ID; all elements go through
+        one vocabulary lookup."""
+        if hasattr(values, "to_numpy") and not isinstance(values, np.ndarray):
+            values = values.to_numpy()
+        L = self.sequence_length
+        if isinstance(values, np.ndarray) and values.ndim == 2 and values.dtype.kind != "O":
+            seqs = [row.tolist() for row in values]
+        else:
+            seqs = [self._elements(seq) for seq in values]
+        seqs = [seq[-L:] for seq in seqs]
+        out = np.full((len(seqs), L), self.PAD_ID, dtype=np.int32)
+        lens = np.fromiter((len(seq) for seq in seqs), dtype=np.int64, count=len(seqs))
+        if lens.sum():
+            flat = self._native.encode([v for seq in seqs for v in seq], num_threads)
+            out[np.arange(L)[None, :] < lens[:, None]] = flat
+        return out
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -157,8 +225,13 @@ class Feature:
 
     def __setstate__(self, state):
         state.setdefault("_native", None)
+        # pickles written before sequence features
+        state.setdefault("sequence_length", None)
+        state.setdefault("pooling", "mean")
         self.__dict__.update(state)
 
     def __repr__(self) -> str:
         return (f"Feature({self.name!r}, {self.dtype}, {self.feature_family}, "
-                f"embedding_size={self.embedding_size})")
+                f"embedding_size={self.embedding_size}"
+                + (f", sequence_length={self.sequence_length}, pooling={self.pooling!r})" if self.is_sequence
+                   else ")"))

@@ -846,6 +846,80 @@ typedef struct {
 } tt_l2norm_grad_job;
 int tt_l2norm_rows_grad(const tt_l2norm_grad_job* jobs, int32_t num_jobs, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Sequence features: pooled embedding bags (Keras Embedding + masked pooling,
+ * TF safe_embedding_lookup_sparse(combiner=...); the reference has no such
+ * feature).  A bag is the L id slots of one example for one sequence
+ * feature; slot l of example b is ids[b * ids_row_stride + l *
+ * ids_pos_stride] (strides in elements, so a [batch, L] tensor and the
+ * transposed view of an [L, batch] block are both read in place).  A slot is
+ * valid when 0 <= id < num_rows (row 0, the OOV row, is valid); the padding
+ * id is -1 and any other id out of range is treated like padding.  cnt_b is
+ * the number of valid slots of example b.  1..TT_BAG_MAX_JOBS jobs (every
+ * sequence feature of every tower of the call) in ONE launch; stream-ordered,
+ * no workspace, no allocation, no synchronisation, no atomics.
+ *
+ * tt_gather_bag, per example b of each job:
+ *   s = ((row(l0) + row(l1)) + ...) over the valid slots in slot order, in
+ *   fp32, one IEEE add per step;  scale = 1 (sum), 1 / cnt (mean) or
+ *   1 / sqrt(cnt) (sqrtn), IEEE division and square root, and 0 when cnt = 0;
+ *   out[b, col_offset : col_offset + dim] = s * scale (sum: s itself, no
+ *   multiply);  an empty bag writes +0.0;  scale_out[b] = scale.
+ * Columns outside the job's range are not touched.
+ * tt_bag_grad_expand, per lookup j = b * L + l of each job:
+ *   ids_flat[j] = id if the slot is valid, else -1;  for a valid slot
+ *   grad[j, 0:dim] = dout[b, col_offset : col_offset + dim] * scale[b] (one
+ *   fp32 multiply; a copy for sum).  Rows of invalid slots are not written.
+ * (ids_flat, grad) is then a flat sparse problem of batch * L lookups for
+ * tt_sparse_adagrad / tt_sparse_adam: one source, grad_ld = dim,
+ * grad_col_offset = 0.
+ * Determinism: every output element is formed by one lane in slot order, so
+ * a bag's result depends only on that bag: not on batch, on addresses or
+ * leading dimensions (16-byte accesses are used only where base and leading
+ * dimension allow them, with the same element order), on which job holds it
+ * or on the other jobs.  A two-job launch equals two one-job launches.
+ * TT_ERR_BAD_ARG (checked on the host before any launch): NULL jobs,
+ * num_jobs outside 1..TT_BAG_MAX_JOBS, a NULL table, L outside 1..1024,
+ * dim < 1, batch * L >= 2^24 (tt_sparse's lookup bound), an empty table, an
+ * unknown pooling, a negative id stride, columns outside the leading
+ * dimension, or (batch > 0) a NULL pointer.  dim > 1024: TT_ERR_UNSUPPORTED.
+ * batch == 0: TT_OK, no work. */
+#define TT_BAG_MAX_JOBS 8
+#define TT_BAG_SUM 0
+#define TT_BAG_MEAN 1
+#define TT_BAG_SQRTN 2
+typedef struct {
+  const float* table;      /* [num_rows, dim], contiguous */
+  int64_t num_rows;
+  int32_t dim;
+  int32_t L;
+  const int32_t* ids;
+  int64_t ids_row_stride;
+  int64_t ids_pos_stride;
+  int32_t pooling;         /* TT_BAG_SUM / TT_BAG_MEAN / TT_BAG_SQRTN */
+  int32_t col_offset;
+  float* out;              /* [batch, out_stride] */
+  int64_t out_stride;
+  float* scale_out;        /* [batch] */
+} tt_bag_job;
+int tt_gather_bag(const tt_bag_job* jobs, int32_t num_jobs, int64_t batch, tt_stream_t stream);
+typedef struct {
+  int64_t num_rows;
+  int32_t dim;
+  int32_t L;
+  const int32_t* ids;
+  int64_t ids_row_stride;
+  int64_t ids_pos_stride;
+  int32_t pooling;
+  int32_t col_offset;
+  const float* dout;       /* [batch, dout_stride] */
+  int64_t dout_stride;
+  const float* scale;      /* [batch], tt_gather_bag's scale_out */
+  int32_t* ids_flat;       /* [batch * L] */
+  float* grad;             /* [batch * L, dim], contiguous */
+} tt_bag_grad_job;
+int tt_bag_grad_expand(const tt_bag_grad_job* jobs, int32_t num_jobs, int64_t batch, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
