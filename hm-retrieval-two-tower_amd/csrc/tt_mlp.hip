@@ -23,9 +23,16 @@
 // masked, split into hi/lo and written to a double-buffered XOR-swizzled LDS
 // tile, read back as A fragments with conflict-free ds_read_b128.  The main
 // loop is branch-free (the image is zero-padded to whole stages and to 4
-// column blocks per wave row), so the compiler's vmcnt waits are exact.
+// column blocks per wave row), so the compiler's vmcnt waits are exact; the
+// two stages it asks for past the last are offset past the descriptor's range
+// and cost no traffic (fetch_a).
 // 4 waves; wave w computes rows 0..63 x the 32-column blocks w, w+4, w+8
 // (each B fragment is loaded by exactly one wave of the workgroup).
+// Epilogue: the operands that do not depend on the accumulators are in flight
+// before they are needed — the bias before the main loop, a thread's whole
+// share of the epilogue mask (8 NCB 16-B loads) before the accumulators go
+// through LDS — and the stores are 8 NCB unrolled trips of range-checked
+// buffer stores: no per-trip division, branch or wait on the previous store.
 //
 // N > 384 (a workgroup keeps at most 3 blocks per wave = 384 columns in
 // accumulators and a 97 KiB output tile): the launch covers (row blocks) x
@@ -94,9 +101,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t mlp_desc(const void* base, uin
                                            static_cast<int>(bytes > 0x7fffffffull ? 0x7fffffffu : bytes),
                                            0x00020000);
 }
+// added to a byte offset: past the range of every mlp_desc descriptor
+constexpr unsigned kMlpPastEnd = 0x80000000u;
+constexpr int64_t kMlpMaxPitch = int64_t(1) << 22;  // widest C / cmask pitch of the epilogue's vector stores
 
 __device__ __forceinline__ f32x4 mlp_load4(__amdgpu_buffer_rsrc_t d, unsigned voff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(d, voff, 0, 0));
+}
+// range-checked like the loads: a store past the descriptor's range is dropped
+__device__ __forceinline__ void mlp_store4(__amdgpu_buffer_rsrc_t d, unsigned voff, f32x4 v) {
+  using raw4 = decltype(__builtin_amdgcn_raw_buffer_load_b128(d, 0u, 0, 0));
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(raw4, v), d, voff, 0, 0);
 }
 // voff per lane (loop-invariant), soff uniform (e.g. the stage's row offset)
 __device__ __forceinline__ f32x4 mlp_load4s(__amdgpu_buffer_rsrc_t d, unsigned voff, unsigned soff) {
@@ -151,13 +166,21 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   const __amdgpu_buffer_rsrc_t da = mlp_desc(a.A + m0 * a.lda, static_cast<uint64_t>(a.M - m0) * a.lda * 4);
   const __amdgpu_buffer_rsrc_t dm = mlp_desc(HAS_MASK ? a.amask + m0 * a.ldam : a.A, static_cast<uint64_t>(a.M - m0) * a.ldam * 4);
   f32x4 ra[2][kMlpUQ], rm[2][kMlpUQ];
+  const int nstage = (a.K + kMlpBK - 1) / kMlpBK;  // KSp = 4 nstage
+  // The loop prefetches two stages ahead without a branch, so it asks for two
+  // stages past the last.  The descriptors span the rest of the matrix (those
+  // depths are the next rows' data), so a stage at or past nstage gets
+  // kMlpPastEnd added to its offsets (a wave-uniform select): past every
+  // descriptor's range (mlp_desc caps it at 2^31 - 1), the loads return zeros
+  // without memory traffic.
   auto fetch_a = [&](int k0, auto slot_c) {
     constexpr int SL = decltype(slot_c)::value;
+    const unsigned ko = static_cast<unsigned>(k0) * 4 + (k0 < nstage * kMlpBK ? 0u : kMlpPastEnd);
 #pragma unroll
     for (int u = 0; u < kMlpUQ; ++u) {
       const int row = qrow + 16 * u;
-      ra[SL][u] = mlp_load4(da, static_cast<unsigned>((row * a.lda + k0 + qk) * 4));
-      if constexpr (HAS_MASK) rm[SL][u] = mlp_load4(dm, static_cast<unsigned>((row * a.ldam + k0 + qk) * 4));
+      ra[SL][u] = mlp_load4(da, static_cast<unsigned>((row * a.lda + qk) * 4) + ko);
+      if constexpr (HAS_MASK) rm[SL][u] = mlp_load4(dm, static_cast<unsigned>((row * a.ldam + qk) * 4) + ko);
     }
   };
   auto stash_a = [&](int k0, auto slot_c, int buf) {
@@ -203,8 +226,15 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
 #pragma unroll
     for (int i = 0; i < NCB; ++i) acc[rb][i] = f32x16{};
 
-  const int nstage = (a.K + kMlpBK - 1) / kMlpBK;  // KSp = 4 nstage
-  const int ks_end = (a.K + 15) / 16;               // k-steps holding data
+  const int ks_end = (a.K + 15) / 16;  // k-steps holding data
+  // the epilogue's bias, issued here so its round trip passes under the main loop
+  const int c0 = GROUPED ? cb0 * 32 : 0;  // first column of the group: tile column c is column c0 + c
+  float bias[NCB];
+#pragma unroll
+  for (int i = 0; i < NCB; ++i) {
+    const int col = c0 + (wave + 4 * i) * 32 + l32;
+    bias[i] = (a.bias && col < a.N) ? a.bias[col] : 0.0f;
+  }
   load_b(0, std::integral_constant<int, 0>());
   load_b(1, std::integral_constant<int, 1>());
   load_b(2, std::integral_constant<int, 2>());
@@ -257,13 +287,58 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   // acc (+ bias, relu) -> LDS tile [64][OUT_LD] (column = 32 cb + l32 of this
   // wave's blocks, in block order cb = wave + 4 i), then row-contiguous vector
   // stores of C with the epilogue mask read the same way (coalesced).
+  const int64_t rows = a.M - m0 < kMlpBM ? a.M - m0 : kMlpBM;
+  float* C = a.C + m0 * a.ldc + c0;
+  const float* cm = a.cmask ? a.cmask + m0 * a.ldcm + c0 : nullptr;
+  // this workgroup's columns: all N, or the group's (c0 is a multiple of 128,
+  // so the group's rows are 16-B aligned exactly when the problem's are)
+  const int N = GROUPED ? (a.N - c0 < NCB * 128 ? a.N - c0 : NCB * 128) : a.N;
+  // 16-B stores of whole rows; a ragged N writes its row's padding columns
+  // (zeros: the image is zero there) when the row pitch has room for them
+  // (pitches below kMlpMaxPitch: 64 rows' byte offsets stay below 2^31)
+  const int n4 = (N + 3) / 4 * 4;
+  const bool v4 = (a.ldc % 4 == 0) && (a.ldc >= c0 + n4) && (a.ldc < kMlpMaxPitch) &&
+                  (reinterpret_cast<uintptr_t>(a.C) % 16 == 0) &&
+                  (!cm || ((N % 4 == 0) && (a.ldcm % 4 == 0) && (a.ldcm < kMlpMaxPitch) &&
+                           (reinterpret_cast<uintptr_t>(a.cmask) % 16 == 0)));
+  // Vector trips: a thread's trip t is 16-B element tid + 256 t of the
+  // [rows][n4 / 4] tile, row-major.  The tile has at most 64 x 32 NCB
+  // elements, so kEpiTrips = 8 NCB trips cover it and the loops unroll fully;
+  // (row, col) start from one division and step by constants of the launch.
+  // A trip past the last row loads and stores at kMlpPastEnd: the mask reads
+  // zeros without traffic, the store is dropped.
+  constexpr int kEpiTrips = 8 * NCB;
+  const int per_row = n4 / 4;
+  const int drow = kMlpThreads / per_row, dcol = kMlpThreads - drow * per_row;
+  const int row0 = tid / per_row, col0 = tid - row0 * per_row;
+  const int nrows = static_cast<int>(rows);
+  auto next_trip = [&](int& row, int& col) {
+    row += drow;
+    col += dcol;
+    if (col >= per_row) {
+      col -= per_row;
+      ++row;
+    }
+  };
+  // the epilogue mask of the thread's whole share, issued before the
+  // accumulators go through LDS: one exposed round trip instead of one per trip
+  f32x4 mk[kEpiTrips];
+  if (v4 && cm) {
+    const __amdgpu_buffer_rsrc_t dcm = mlp_desc(cm, static_cast<uint64_t>((rows - 1) * a.ldcm + N) * 4);
+    const unsigned ldcm4 = static_cast<unsigned>(a.ldcm) * 4;
+    int row = row0, col = col0;
+#pragma unroll
+    for (int t = 0; t < kEpiTrips; ++t) {
+      mk[t] = mlp_load4(dcm, row < nrows ? row * ldcm4 + col * 16 : kMlpPastEnd);
+      next_trip(row, col);
+    }
+  }
   __syncthreads();  // every wave is done reading the A stages
   float* tile = reinterpret_cast<float*>(smem_raw);
-  const int c0 = GROUPED ? cb0 * 32 : 0;  // first column of the group: tile column c is column c0 + c
 #pragma unroll
   for (int i = 0; i < NCB; ++i) {
     const int col = (wave + 4 * i) * 32 + l32;
-    const float b = (a.bias && c0 + col < a.N) ? a.bias[c0 + col] : 0.0f;
+    const float b = bias[i];
 #pragma unroll
     for (int rb = 0; rb < kMlpRB; ++rb)
 #pragma unroll
@@ -274,30 +349,28 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
       }
   }
   __syncthreads();
-  const int64_t rows = a.M - m0 < kMlpBM ? a.M - m0 : kMlpBM;
-  float* C = a.C + m0 * a.ldc + c0;
-  const float* cm = a.cmask ? a.cmask + m0 * a.ldcm + c0 : nullptr;
-  // this workgroup's columns: all N, or the group's (c0 is a multiple of 128,
-  // so the group's rows are 16-B aligned exactly when the problem's are)
-  const int N = GROUPED ? (a.N - c0 < NCB * 128 ? a.N - c0 : NCB * 128) : a.N;
-  // 16-B stores of whole rows; a ragged N writes its row's padding columns
-  // (zeros: the image is zero there) when the row pitch has room for them
-  const int n4 = (N + 3) / 4 * 4;
-  const bool v4 = (a.ldc % 4 == 0) && (a.ldc >= c0 + n4) && (reinterpret_cast<uintptr_t>(a.C) % 16 == 0) &&
-                  (!cm || ((N % 4 == 0) && (a.ldcm % 4 == 0) && (reinterpret_cast<uintptr_t>(a.cmask) % 16 == 0)));
   if (v4) {
-    const int per_row = n4 / 4;
-    for (int idx = tid; idx < rows * per_row; idx += kMlpThreads) {
-      const int row = idx / per_row, c4 = (idx - row * per_row) * 4;
-      f32x4 v = *reinterpret_cast<const f32x4*>(tile + row * OUT_LD + c4);
-      if (cm) {
-        const f32x4 mk = *reinterpret_cast<const f32x4*>(cm + row * a.ldcm + c4);
+    const __amdgpu_buffer_rsrc_t dc = mlp_desc(C, static_cast<uint64_t>((rows - 1) * a.ldc + n4) * 4);
+    const unsigned ldc4 = static_cast<unsigned>(a.ldc) * 4;
+    auto store_rows = [&](auto masked_c) {
+      constexpr bool MASKED = decltype(masked_c)::value;
+      int row = row0, col = col0;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = mk[e] > 0.0f ? v[e] : 0.0f;
-        if (a.parts) *reinterpret_cast<f32x4*>(tile + row * OUT_LD + c4) = v;  // masked, for the column sums
+      for (int t = 0; t < kEpiTrips; ++t) {
+        const bool live = row < nrows;
+        float* at = tile + (live ? row : 0) * OUT_LD + col * 4;
+        f32x4 v = *reinterpret_cast<const f32x4*>(at);
+        if constexpr (MASKED) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = mk[t][e] > 0.0f ? v[e] : 0.0f;
+          if (a.parts && live) *reinterpret_cast<f32x4*>(at) = v;  // masked, for the column sums
+        }
+        mlp_store4(dc, live ? row * ldc4 + col * 16 : kMlpPastEnd, v);
+        next_trip(row, col);
       }
-      *reinterpret_cast<f32x4*>(C + row * a.ldc + c4) = v;
-    }
+    };
+    if (cm) store_rows(std::true_type());
+    else store_rows(std::false_type());
   } else {
     for (int idx = tid; idx < rows * N; idx += kMlpThreads) {
       const int row = idx / N, c = idx - row * N;
@@ -761,6 +834,15 @@ __device__ __forceinline__ void mlp_sum_parts_block(const float* __restrict__ pa
   const int per = (S + 15) / 16;
   const int s0 = grp * per, s1 = min(S, s0 + per);
   f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  // the Adagrad operands of the threads that apply it (group 0) do not depend
+  // on the sum: loaded with the partials, not in a round trip of their own
+  // after it (the plain sum, ad.param == NULL, loads nothing here)
+  const bool apply = ad.param != nullptr && grp == 0 && e4 < len;
+  f32x4 pa = {0.0f, 0.0f, 0.0f, 0.0f}, ac = pa;
+  if (apply) {
+    pa = *reinterpret_cast<const f32x4*>(ad.param + e4);
+    ac = *reinterpret_cast<const f32x4*>(ad.accum + e4);
+  }
   if (e4 < len) {
     f32x4 v[8];
     for (int sb = s0; sb < s1; sb += 8) {
@@ -785,9 +867,7 @@ __device__ __forceinline__ void mlp_sum_parts_block(const float* __restrict__ pa
       for (int q = 0; q < 4; ++q) t[q] += r[q];
     }
     *reinterpret_cast<f32x4*>(out + e4) = t;
-    if (ad.param) {
-      f32x4 pa = *reinterpret_cast<const f32x4*>(ad.param + e4);
-      f32x4 ac = *reinterpret_cast<const f32x4*>(ad.accum + e4);
+    if (apply) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float gi = t[q];
