@@ -1,5 +1,6 @@
 // K14 recall hits, the per-shard top-k merge and the per-query exclusion
-// filter of sorted top-k lists; the loss reduction.
+// filter of sorted top-k lists; set-valued ranking metrics (MAP@K, NDCG@K,
+// MRR, recall) of ranked lists; the loss reduction.
 //
 // tt_recall_hits restates IndexRecall.__call__
 // (/root/reference/pkg/modelling/metrics/index_recall.py:52-58):
@@ -269,6 +270,258 @@ __global__ void __launch_bounds__(256) topk_exclude_kernel(const float* __restri
   if (t == 0 && n_kept) n_kept[q] = kept;
 }
 
+// ---- tt_rank_metrics --------------------------------------------------------
+// Set-valued ranking metrics of one ranked list against one truth row, in
+// O(T + k_list) per query with no sort.  The distinct valid truth ids go into
+// an open-addressing hash table in LDS (>= 2 * T slots, linear probing;
+// inserting with atomicCAS counts them, which is m).  Every list position
+// probes the table and atomicMin's itself into the slot of its id, so a slot
+// ends up holding the FIRST position of that id: the hit positions are a
+// function of membership alone, whatever order the LDS atomics land in.  The
+// slots then set one bit per hit position; one wave turns the (at most 64 x
+// 64-bit) bitmap into the ascending list of hit positions with popcount
+// prefixes, and lane j < num_ks walks that list up to ks[j] — the sequential
+// fp32 sums the contract fixes, at most min(m, k) trips.
+//
+// As for topk_exclude_kernel: NW = 1 runs four queries per 256-thread
+// workgroup, each wave on its own LDS region with no workgroup barrier
+// (T <= 64 and k_list <= 256: at most 1.3 KB per wave, so the
+// 32-waves-per-CU cap stays the limit); NW = 4 runs one query per workgroup
+// (at most 2 x 8 KB table + 512 B bitmap + 4 KB hit list).
+constexpr int kRankMaxK = 4096;
+constexpr int kRankMaxT = 1024;
+constexpr int kRankSmallK = 256;
+constexpr int kRankSmallT = 64;
+constexpr int kRankNoPos = 0x7FFFFFFF;
+
+struct RankArgs {
+  const int32_t* cand;
+  int64_t ld_cand;
+  const int32_t* truth;
+  int64_t ld_truth;
+  int64_t n_queries;
+  int32_t k_list;
+  int32_t T;
+  int32_t num_ks;
+  int32_t ks[kMaxKs];
+  const float* disc;
+  const float* idcg;
+  float* vals;
+  int32_t* hits;
+  int32_t* m_out;
+  unsigned long long* n_valid;
+  int32_t log2p;
+  int32_t group_bytes;
+};
+
+// LDS of one group: keys [P] int, first positions [P] int, the hit bitmap
+// (64 bits per 64 list positions), the hit list [min(T, k_list)] int, then
+// (16-B aligned) the per-wave distinct counts.
+inline int rank_group_bytes(int k_list, int T, int log2p) {
+  const int64_t words = (k_list + 63) / 64;
+  const int64_t hit_cap = T < k_list ? T : k_list;
+  return static_cast<int>(round_up((int64_t{1} << log2p) * 8 + words * 8 + hit_cap * 4, 16)) + 16;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(256) rank_metrics_kernel(const RankArgs a) {
+  extern __shared__ __align__(16) unsigned char rank_lds[];
+  constexpr int NT = NW * kWave;
+  const int wave = static_cast<int>(threadIdx.x) / kWave;
+  const int lane = lane_id();
+  const int64_t q = NW == 1 ? blockIdx.x * 4ll + wave : static_cast<int64_t>(blockIdx.x);
+  if (q >= a.n_queries) return;  // NW = 1 only: a whole wave, and no workgroup barrier follows
+  const int t = NW == 1 ? lane : static_cast<int>(threadIdx.x);
+  unsigned char* base = rank_lds + (NW == 1 ? wave * a.group_bytes : 0);
+  const int P = 1 << a.log2p;
+  const int words = (a.k_list + 63) / 64;
+  int* keys = reinterpret_cast<int*>(base);
+  int* first = keys + P;
+  unsigned* bits = reinterpret_cast<unsigned*>(first + P);
+  int* hitpos = reinterpret_cast<int*>(bits + 2 * words);
+  int* wcnt = reinterpret_cast<int*>(base + a.group_bytes - 16);
+  const unsigned mask = static_cast<unsigned>(P - 1);
+  const int shift = 32 - a.log2p;  // log2p >= 1
+  auto slot_of = [&](int32_t v) { return (static_cast<unsigned>(v) * 2654435761u) >> shift; };
+  auto valid = [](int32_t v) { return v >= 0 && v != kPadIndex; };
+
+  for (int j = t; j < P; j += NT) {
+    keys[j] = -1;
+    first[j] = kRankNoPos;
+  }
+  for (int j = t; j < 2 * words; j += NT) bits[j] = 0u;
+  group_sync<NW>();
+  // at most T inserts into >= 2 * T slots: every probe sequence ends
+  const int32_t* tr = a.truth + q * a.ld_truth;
+  int mine = 0;
+  for (int j = t; j < a.T; j += NT) {
+    const int32_t v = tr[j];
+    if (!valid(v)) continue;
+    unsigned s = slot_of(v);
+    for (;;) {
+      const int old = atomicCAS(&keys[s], -1, v);
+      if (old == -1) ++mine;  // this thread's insert: a new distinct id
+      if (old == -1 || old == v) break;
+      s = (s + 1) & mask;
+    }
+  }
+  int m = wave_sum_i32(mine);
+  if constexpr (NW > 1) {
+    if (lane == 0) wcnt[wave] = m;
+    __syncthreads();
+    m = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) m += wcnt[w];
+  } else {
+    group_sync<NW>();
+  }
+  if (m == 0) {  // no truth (uniform over the group): zeros, and the query is in no average
+    for (int j = t; j < a.num_ks; j += NT) {
+      float* v = a.vals + (q * a.num_ks + j) * 4;
+      v[0] = v[1] = v[2] = v[3] = 0.0f;
+      a.hits[q * a.num_ks + j] = 0;
+    }
+    if (t == 0 && a.m_out) a.m_out[q] = 0;
+    return;
+  }
+  const int32_t* li = a.cand + q * a.ld_cand;
+  for (int j = t; j < a.k_list; j += NT) {
+    const int32_t v = li[j];
+    if (!valid(v)) continue;
+    unsigned s = slot_of(v);
+    for (;;) {
+      const int key = keys[s];
+      if (key == v) atomicMin(&first[s], j);
+      if (key == v || key == -1) break;
+      s = (s + 1) & mask;
+    }
+  }
+  group_sync<NW>();
+  for (int j = t; j < P; j += NT) {
+    const int p = first[j];
+    if (p != kRankNoPos) atomicOr(&bits[p >> 5], 1u << (p & 31));
+  }
+  group_sync<NW>();
+  if (NW > 1 && wave != 0) return;
+
+  // one wave: lane l owns list positions [64 l, 64 l + 64)
+  unsigned long long w = 0ull;
+  if (lane < words) w = (static_cast<unsigned long long>(bits[2 * lane + 1]) << 32) | bits[2 * lane];
+  const int cnt = __popcll(w);
+  int incl = cnt;
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const int o = __shfl_up(incl, d, kWave);
+    if (lane >= d) incl += o;
+  }
+  const int n_hits = __shfl(incl, kWave - 1, kWave);  // <= min(m, k_list): distinct truth ids, distinct positions
+  int at = incl - cnt;
+  while (w) {
+    hitpos[at++] = lane * 64 + static_cast<int>(__builtin_ctzll(w));
+    w &= w - 1;
+  }
+  group_sync<1>();
+
+  if (lane < a.num_ks) {
+    int k = a.ks[0];
+#pragma unroll
+    for (int j = 1; j < kMaxKs; ++j) k = lane == j ? a.ks[j] : k;
+    int c = 0, f = 0;
+    float ap = 0.0f, dcg = 0.0f;
+    for (int n = 0; n < n_hits; ++n) {
+      const int p = hitpos[n];
+      if (p >= k) break;
+      ++c;
+      ap = ap + static_cast<float>(c) / static_cast<float>(p + 1);
+      dcg = dcg + a.disc[p];
+      if (n == 0) f = p + 1;
+    }
+    const int mk = m < k ? m : k;
+    float* v = a.vals + (q * a.num_ks + lane) * 4;
+    v[0] = static_cast<float>(c) / static_cast<float>(m);
+    v[1] = ap / static_cast<float>(mk);
+    v[2] = dcg / a.idcg[mk];
+    v[3] = f ? 1.0f / static_cast<float>(f) : 0.0f;
+    a.hits[q * a.num_ks + lane] = c;
+  }
+  if (lane == 0) {
+    if (a.m_out) a.m_out[q] = m;
+    if (a.n_valid) atomicAdd(a.n_valid, 1ull);
+  }
+}
+
+// The accumulators' second launch.  Workgroup b < 4 * num_ks owns (j, metric) =
+// (b / 4, b % 4): thread t adds the fp32 values of queries t, t + 256, ... in
+// ascending order as doubles, a fixed LDS tree follows, then acc += x[0] — no
+// floating-point atomics, so the sums are the same bits every run.  A query
+// with m = 0 holds +0.0f in every slot, and s + 0.0 == s for every s these
+// sums reach (they start at +0.0), so adding it is skipping it.  Workgroup
+// 4 * num_ks + j sums hits@k and counts the queries with a hit (integers);
+// one more counts the queries with m > 0 when the caller asked for m.
+__global__ void __launch_bounds__(256) rank_reduce_kernel(const float* __restrict__ vals,
+                                                          const int32_t* __restrict__ hits, int64_t n_queries,
+                                                          int num_ks, double* __restrict__ acc_f64,
+                                                          unsigned long long* __restrict__ acc_i64,
+                                                          const int32_t* __restrict__ m,
+                                                          unsigned long long* __restrict__ n_valid) {
+  __shared__ double x[256];
+  __shared__ unsigned long long xs[256], xc[256];
+  const int t = static_cast<int>(threadIdx.x);
+  const int b = static_cast<int>(blockIdx.x);
+  if (b < 4 * num_ks) {
+    const float* src = vals + b;  // (q * num_ks + j) * 4 + metric with b = 4 j + metric
+    const int64_t stride = 4ll * num_ks;
+    constexpr int kAhead = 16;  // loads in flight per lane; the additions keep their order
+    double s = 0.0;
+    int64_t qi = t;
+    for (; qi + (kAhead - 1) * 256ll < n_queries; qi += kAhead * 256ll) {
+      float v[kAhead];
+#pragma unroll
+      for (int u = 0; u < kAhead; ++u) v[u] = src[(qi + u * 256ll) * stride];
+#pragma unroll
+      for (int u = 0; u < kAhead; ++u) s += static_cast<double>(v[u]);
+    }
+    for (; qi < n_queries; qi += 256) s += static_cast<double>(src[qi * stride]);
+    x[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) x[t] += x[t + w];
+      __syncthreads();
+    }
+    if (t == 0) acc_f64[b] += x[0];
+  } else {
+    // j < num_ks: column j of hits; j == num_ks (launched only with m): the scored queries, counted in xc
+    const int j = b - 4 * num_ks;
+    const int32_t* src = j < num_ks ? hits + j : m;
+    const int64_t stride = j < num_ks ? num_ks : 1;
+    unsigned long long s = 0ull, c = 0ull;
+#pragma unroll 8
+    for (int64_t qi = t; qi < n_queries; qi += 256) {
+      const int32_t h = src[qi * stride];
+      s += static_cast<unsigned long long>(h);
+      c += h > 0 ? 1ull : 0ull;
+    }
+    xs[t] = s;
+    xc[t] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) {
+        xs[t] += xs[t + w];
+        xc[t] += xc[t + w];
+      }
+      __syncthreads();
+    }
+    if (t == 0) {
+      if (j < num_ks) {
+        acc_i64[2 * j] += xs[0];
+        acc_i64[2 * j + 1] += xc[0];
+      } else {
+        n_valid[0] += xc[0];
+      }
+    }
+  }
+}
+
 }  // namespace
 }  // namespace tt
 
@@ -295,6 +548,66 @@ extern "C" int tt_recall_hits(const int32_t* true_ids, const int32_t* cand_ids, 
   a.hits = reinterpret_cast<unsigned long long*>(hits);
   hipLaunchKernelGGL(recall_hits_kernel, dim3(ceil_div(batch, 256)), dim3(256), 0, to_stream(stream), a);
   TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int tt_rank_metrics(const int32_t* cand, int64_t ld_cand, int32_t k_list, const int32_t* truth,
+                               int64_t ld_truth, int32_t T, int64_t n_queries, const int32_t* ks_host, int32_t num_ks,
+                               const float* disc, const float* idcg, float* vals, int32_t* hits, int32_t* m_out,
+                               double* acc_f64, int64_t* acc_i64, int64_t* n_valid, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(k_list >= 1 && k_list <= kRankMaxK, "tt_rank_metrics: k_list=%d outside [1,%d]", k_list, kRankMaxK);
+  TT_REQUIRE(T >= 1 && T <= kRankMaxT, "tt_rank_metrics: T=%d outside [1,%d]", T, kRankMaxT);
+  TT_REQUIRE(num_ks >= 1 && num_ks <= kMaxKs, "tt_rank_metrics: num_ks=%d outside [1,%d]", num_ks, kMaxKs);
+  TT_REQUIRE(ks_host != nullptr, "tt_rank_metrics: NULL ks_host");
+  for (int j = 0; j < num_ks; ++j)
+    TT_REQUIRE(ks_host[j] >= 1 && ks_host[j] <= k_list, "tt_rank_metrics: ks[%d]=%d outside [1, k_list=%d]", j,
+               ks_host[j], k_list);
+  TT_REQUIRE(ld_cand >= k_list, "tt_rank_metrics: ld_cand=%lld below k_list=%d", static_cast<long long>(ld_cand),
+             k_list);
+  TT_REQUIRE(ld_truth >= T, "tt_rank_metrics: ld_truth=%lld below T=%d", static_cast<long long>(ld_truth), T);
+  TT_REQUIRE(n_queries >= 0 && n_queries <= INT32_MAX, "tt_rank_metrics: n_queries outside [0, 2^31)");
+  const int n_acc = (acc_f64 != nullptr) + (acc_i64 != nullptr) + (n_valid != nullptr);
+  TT_REQUIRE(n_acc == 0 || n_acc == 3, "tt_rank_metrics: acc_f64, acc_i64 and n_valid go together (all or none)");
+  if (n_queries == 0) return TT_OK;
+  TT_REQUIRE(cand != nullptr, "tt_rank_metrics: NULL cand");
+  TT_REQUIRE(truth != nullptr, "tt_rank_metrics: NULL truth");
+  TT_REQUIRE(disc != nullptr && idcg != nullptr, "tt_rank_metrics: NULL disc / idcg table");
+  TT_REQUIRE(vals != nullptr, "tt_rank_metrics: NULL vals");
+  TT_REQUIRE(hits != nullptr, "tt_rank_metrics: NULL hits");
+  RankArgs a{};
+  a.cand = cand;
+  a.ld_cand = ld_cand;
+  a.truth = truth;
+  a.ld_truth = ld_truth;
+  a.n_queries = n_queries;
+  a.k_list = k_list;
+  a.T = T;
+  a.num_ks = num_ks;
+  for (int j = 0; j < num_ks; ++j) a.ks[j] = ks_host[j];
+  a.disc = disc;
+  a.idcg = idcg;
+  a.vals = vals;
+  a.hits = hits;
+  a.m_out = m_out;
+  // with m_out the reduction counts the scored queries from it; without, each scored query adds itself
+  a.n_valid = m_out ? nullptr : reinterpret_cast<unsigned long long*>(n_valid);
+  a.log2p = 1;
+  while ((1 << a.log2p) < 2 * T) ++a.log2p;
+  a.group_bytes = rank_group_bytes(k_list, T, a.log2p);
+  if (k_list <= kRankSmallK && T <= kRankSmallT) {
+    hipLaunchKernelGGL(rank_metrics_kernel<1>, dim3(ceil_div(n_queries, 4)), dim3(256), 4 * a.group_bytes,
+                       to_stream(stream), a);
+  } else {
+    hipLaunchKernelGGL(rank_metrics_kernel<4>, dim3(n_queries), dim3(256), a.group_bytes, to_stream(stream), a);
+  }
+  TT_CHECK_LAUNCH();
+  if (n_acc) {
+    hipLaunchKernelGGL(rank_reduce_kernel, dim3(5 * num_ks + (m_out ? 1 : 0)), dim3(256), 0, to_stream(stream), vals,
+                       hits, n_queries, num_ks, acc_f64, reinterpret_cast<unsigned long long*>(acc_i64), m_out,
+                       reinterpret_cast<unsigned long long*>(n_valid));
+    TT_CHECK_LAUNCH();
+  }
   return TT_OK;
 }
 

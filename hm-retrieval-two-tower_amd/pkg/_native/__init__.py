@@ -405,6 +405,10 @@ _PROTOS = {
     "tt_topk_exclude": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
     "tt_recall_hits": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "tt_rank_metrics": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int64, POINTER(c_int32), c_int32, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tt_vocab_create": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
     "tt_vocab_size": (c_int64, [c_void_p]),
     "tt_vocab_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32]),

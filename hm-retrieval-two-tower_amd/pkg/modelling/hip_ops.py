@@ -51,6 +51,8 @@ __all__ = [
     "topk_merge",
     "topk_exclude",
     "recall_hits",
+    "rank_metrics",
+    "rank_discount_tables",
     "Workspace",
     "capture_guard",
     "CaptureTopology",
@@ -1134,6 +1136,79 @@ def recall_hits(true_ids: torch.Tensor, cand_ids: torch.Tensor, ks: Sequence[int
     ks_arr = (ctypes.c_int32 * len(ks))(*[int(k) for k in ks])
     check(lib().tt_recall_hits(true_ids.data_ptr(), cand_ids.data_ptr(), B, K, ks_arr, len(ks), hits.data_ptr(),
                                _stream()))
+
+
+_RANK_TABLES: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def rank_discount_tables(k_list: int) -> Tuple["np.ndarray", "np.ndarray"]:
+    """Host fp32 tables of tt_rank_metrics: disc[i] = float32(1 / log2(i + 2))
+    (computed in float64, rounded once) for i < k_list, and idcg[n] = the
+    sequential fp32 sum of disc[:n] (idcg[0] = 0), n <= k_list."""
+    import numpy as np
+
+    disc = (1.0 / np.log2(np.arange(k_list, dtype=np.float64) + 2.0)).astype(np.float32)
+    idcg = np.zeros(k_list + 1, np.float32)
+    np.cumsum(disc, dtype=np.float32, out=idcg[1:])  # cumsum is sequential: one fp32 add per element
+    return disc, idcg
+
+
+def _rank_tables(device: torch.device, k_list: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    key = (device.index if device.index is not None else torch.cuda.current_device(), k_list)
+    if key not in _RANK_TABLES:
+        disc, idcg = rank_discount_tables(k_list)
+        _RANK_TABLES[key] = (torch.as_tensor(disc, device=device), torch.as_tensor(idcg, device=device))
+    return _RANK_TABLES[key]
+
+
+def rank_metrics(cand: torch.Tensor, truth: torch.Tensor, ks: Sequence[int],
+                 acc: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Set-valued ranking metrics (tt_rank_metrics) of ranked lists cand
+    [Q, k_list] int32 against truth [Q, T] (or [Q]: T = 1) int32; values < 0
+    or == INT32_MAX are padding on either side.  Rows may be strided (unit
+    column stride).  Returns (vals [Q, len(ks), 4] fp32 = recall, ap, ndcg, rr
+    at each k; hits [Q, len(ks)] int32; m [Q] int32 = distinct valid truth
+    ids).  acc = (acc_f64 [len(ks), 4] float64, acc_i64 [len(ks), 2] int64,
+    n_valid [1] int64) is added to: the sums of the four values, of hits and
+    of the queries with a hit, and the number of queries with m > 0 (queries
+    with m = 0 are in no sum)."""
+    _req(cand, "cand", torch.int32, 2)
+    if isinstance(truth, torch.Tensor) and truth.dim() == 1:
+        truth = truth.unsqueeze(1)
+    _req(truth, "truth", torch.int32, 2)
+    if truth.device != cand.device:
+        raise ValueError(f"truth must live on cand's device {cand.device} (got {truth.device})")
+    Q, k_list = cand.shape
+    T = truth.shape[1]
+    if truth.shape[0] != Q:
+        raise ValueError(f"truth has {truth.shape[0]} rows, cand {Q}")
+    if not 1 <= k_list <= 4096 or not 1 <= T <= 1024:
+        raise ValueError(f"need 1 <= k_list <= 4096 and 1 <= T <= 1024, got k_list={k_list}, T={T}")
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 16 or any(not 1 <= k <= k_list for k in ks):
+        raise ValueError(f"need 1 to 16 values of k, each in [1, {k_list}], got {ks}")
+    ld_cand, ld_truth = _row_major(cand, "cand"), _row_major(truth, "truth")
+    nk = len(ks)
+    ptrs = [None, None, None]
+    if acc is not None:
+        acc_f64, acc_i64, n_valid = acc
+        _req(acc_f64, "acc_f64", torch.float64)
+        _req(acc_i64, "acc_i64", torch.int64)
+        _req(n_valid, "n_valid", torch.int64)
+        for t, name, n in ((acc_f64, "acc_f64", 4 * nk), (acc_i64, "acc_i64", 2 * nk), (n_valid, "n_valid", 1)):
+            if t.numel() != n or not t.is_contiguous() or t.device != cand.device:
+                raise ValueError(f"{name} must be contiguous with {n} elements on {cand.device}")
+        ptrs = [acc_f64.data_ptr(), acc_i64.data_ptr(), n_valid.data_ptr()]
+    disc, idcg = _rank_tables(cand.device, k_list)
+    vals = torch.empty(Q, nk, 4, dtype=torch.float32, device=cand.device)
+    hits = torch.empty(Q, nk, dtype=torch.int32, device=cand.device)
+    m = torch.empty(Q, dtype=torch.int32, device=cand.device)
+    ks_arr = (ctypes.c_int32 * nk)(*ks)
+    check(lib().tt_rank_metrics(cand.data_ptr(), ld_cand, k_list, truth.data_ptr(), ld_truth, T, Q, ks_arr, nk,
+                                disc.data_ptr(), idcg.data_ptr(), vals.data_ptr(), hits.data_ptr(), m.data_ptr(),
+                                ptrs[0], ptrs[1], ptrs[2], _stream()))
+    return vals, hits, m
 
 
 def batch_take(src: torch.Tensor, perm: torch.Tensor, cursor: torch.Tensor, out: torch.Tensor,

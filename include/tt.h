@@ -653,6 +653,53 @@ int tt_recall_hits(const int32_t* true_ids, const int32_t* cand_ids,
                    int64_t batch, int32_t k_total, const int32_t* ks_host,
                    int32_t num_ks, int64_t* hits, tt_stream_t stream);
 
+/* Ranking metrics on multi-item ground truth: recall@k, AP@k (its mean is
+ * MAP@k, the H&M task's MAP@12), NDCG@k and the reciprocal rank, per query
+ * and for every k = ks[j].  cand is [n_queries][k_list] with row stride
+ * ld_cand (indices or integer identifiers, as tt_bruteforce_search,
+ * tt_topk_merge and tt_topk_exclude write them), truth [n_queries][T] with row
+ * stride ld_truth (both strides in elements).  A value < 0 or == 0x7FFFFFFF
+ * is padding on either side: it matches nothing and is not counted; padding
+ * may sit anywhere in a truth row.
+ *   - m = number of DISTINCT valid truth ids.  Position i (1-based) is a hit,
+ *     h_i = 1, when cand[i] is valid, is in the truth set and i is the first
+ *     list position holding that id (a repeated list entry is credited once);
+ *     c_i = h_1 + ... + h_i.
+ *   - hits[q][j] = c_k (int32), and vals[q][j][0..3] in fp32, one IEEE
+ *     operation per step, no contraction:
+ *       recall = float(c_k) / float(m)
+ *       ap     = (sum over hits i <= k of float(c_i) / float(i)) / float(min(m, k))
+ *       ndcg   = (sum over hits i <= k of disc[i - 1]) / idcg[min(m, k)]
+ *       rr     = 1 / float(first hit) when it is <= k, else 0
+ *     both sums sequential in ascending i, starting from their first term.
+ *   - disc [k_list] and idcg [k_list + 1] are device fp32 tables built by the
+ *     caller (no transcendental runs on the device): disc[i] = float(1 /
+ *     log2(i + 2)) computed in double and rounded once, idcg[0] = 0 and
+ *     idcg[n] the sequential fp32 prefix sum of disc.
+ *   - A query with m = 0 gets zeros in vals and hits, reports m = 0 and is left
+ *     out of every accumulator.  m_out (int32 [n_queries], or NULL) receives m.
+ *   - Accumulators (all three or none), added to like tt_recall_hits' hits:
+ *     acc_f64 double [num_ks][4] += the sums of recall, ap, ndcg, rr; acc_i64
+ *     int64 [num_ks][2] += the sum of c_k and the number of queries with
+ *     c_k > 0; n_valid int64 [1] += the number of queries with m > 0.  The
+ *     double sums are deterministic (a second launch, no floating-point
+ *     atomics): per (j, metric), lane t of 256 adds queries t, t + 256, ... in
+ *     ascending order as doubles, then x[t] += x[t + s] for s = 128 .. 1, then
+ *     acc += x[0].
+ *   - ks is a host array, any order, repeats allowed.  The outputs must not
+ *     overlap the inputs.
+ * Needs 1 <= k_list <= 4096, 1 <= T <= 1024, 1 <= num_ks <= 16, every ks[j]
+ * in [1, k_list], ld_cand >= k_list, ld_truth >= T, 0 <= n_queries < 2^31
+ * (0: TT_OK, no launch) and every pointer but m_out and the accumulators
+ * non-NULL when n_queries > 0.  O(T + k_list) per query, no workspace. */
+int tt_rank_metrics(const int32_t* cand, int64_t ld_cand, int32_t k_list,
+                    const int32_t* truth, int64_t ld_truth, int32_t T,
+                    int64_t n_queries, const int32_t* ks_host, int32_t num_ks,
+                    const float* disc, const float* idcg,
+                    float* vals, int32_t* hits, int32_t* m_out,
+                    double* acc_f64, int64_t* acc_i64, int64_t* n_valid,
+                    tt_stream_t stream);
+
 
 /* ------------------------------------------------------------------------ *
  * K15  Input pipeline.
