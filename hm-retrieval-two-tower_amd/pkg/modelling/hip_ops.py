@@ -77,8 +77,9 @@ def _req(t: torch.Tensor, name: str, dtype: torch.dtype, ndim: Optional[int] = N
 
 def _row_major(t: torch.Tensor, name: str) -> int:
     """Leading dimension of a 2-D tensor with unit column stride."""
-    if t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1):
+    if t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1 and t.numel() > 0):
         raise ValueError(f"{name} must be 2-D with unit column stride")
+    # an empty tensor's strides carry no layout (numpy hands over zeros): nothing is read
     return max(t.stride(0), t.shape[1])
 
 

@@ -599,12 +599,17 @@ def dense_adagrad(param: np.ndarray, accum: np.ndarray, grad: np.ndarray, lr: fl
     param -= (g * lr) / (np.sqrt(accum) + eps)
 
 
+def adam_powers(beta1, beta2, step) -> Tuple[np.float32, np.float32]:
+    """(beta1^step, beta2^step) as the fp32 optimizers compute them (powf)."""
+    f = np.float32
+    return f(np.power(f(beta1), f(step))), f(np.power(f(beta2), f(step)))
+
+
 def dense_adam(param, m, v, grad, lr, beta1, beta2, eps, step) -> None:
     """ResourceApplyAdam (fp32, in place)."""
     f = np.float32
     g = _f32(grad)
-    b1p = f(np.power(f(beta1), f(step)))
-    b2p = f(np.power(f(beta2), f(step)))
+    b1p, b2p = adam_powers(beta1, beta2, step)
     alpha = f((f(lr) * np.sqrt(f(1) - b2p)) / (f(1) - b1p))
     m += (g - m) * (f(1) - f(beta1))
     v += (g * g - v) * (f(1) - f(beta2))
@@ -617,8 +622,7 @@ def sparse_adam(table, m, v, ids, grad, lr, beta1, beta2, eps, step, chunk: int 
     ids = _i32(ids).reshape(-1)
     valid = (ids >= 0) & (ids < table.shape[0])
     uniq, sums = dedup_sum(ids[valid], _f32(grad)[valid], chunk)
-    b1p = f(np.power(f(beta1), f(step)))
-    b2p = f(np.power(f(beta2), f(step)))
+    b1p, b2p = adam_powers(beta1, beta2, step)
     lr_t = f(f(lr) * (np.sqrt(f(1) - b2p) / (f(1) - b1p)))
     m *= f(beta1)
     v *= f(beta2)

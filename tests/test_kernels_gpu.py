@@ -2,6 +2,15 @@
 
 Tolerances:
   gather, dedup, Adagrad, top-k indices + scores, merge, recall: bit-exact.
+  Adam (sparse and dense): here rtol 2e-6 / atol 1e-7 with the default betas
+    (0.9, 0.999: lr_t holds the host's powf, which may differ from numpy's in
+    the last bit); bit-exact in table / p, m and v with betas (0.5, 0.75),
+    whose powers are fp32 numbers (tests/test_sparse_edges_gpu.py).
+  The update's passes after the sort (odd and large dims, > 16 tables, placed
+    segment boundaries), the dense optimizers' grid-stride loops,
+    tt_dense_adagrad_many and tt_gather_tagged: tests/test_sparse_edges_gpu.py,
+    tests/test_gather_tagged_gpu.py (inputs: tests/sparse_cases.py, checked on
+    the CPU by tests/test_sparse_edges_host.py).
   tower GEMMs (tt_mlp_rows, tt_mlp_wgrad) vs fp64: norm-relative 2e-5
     (bf16x3; fp32 accumulation of K products alone is ~sqrt(K) 2^-24).
   in-batch softmax CE (bf16 MFMA operands, fp32 accumulate) vs fp64 oracle:
