@@ -23,8 +23,21 @@
 //     fp32 sums of each segment piece; a segment that starts and ends inside
 //     the block is applied immediately, the pieces of longer segments (Zipf
 //     heavy hitters repeated thousands of times) are written out.
-//  4. join   — the block where a long segment starts adds the pieces of the
-//     following blocks in order and applies the update.
+//  4. join   — inside the same launch, by the LAST block to arrive: a block
+//     that wrote a piece of a segment spanning blocks stores it write-through,
+//     drains its stores and adds 1 to the segment's counter (one counter per
+//     block in the workspace, indexed by the block where the segment starts;
+//     zeroed by the key/sort stage of every call and again by the joiner).
+//     The block whose add returns span - 1 reads every piece past the caches,
+//     adds them in block order starting from the start block's and applies
+//     the update; every other block returns.  Nobody waits, polls or spins,
+//     and the sum does not depend on which block came last.  A piece block
+//     finds its segment's first and last block from probes of the sorted keys
+//     in both directions, one per lane and block, loaded in the same round as
+//     its own keys; a segment reaching past P blocks goes on with a (P+1)-ary
+//     search.  Tables
+//     of at most 255 rows (nearly all pieces, little row traffic) take the
+//     lowest wave indices, so their joins run under the large tables' traffic.
 // Summation order = per table, sorted lookups cut into aligned blocks of
 // kBlock; each piece summed sequentially from 0, pieces added in order from 0.
 // This equals TF's flat order whenever an id occurs within one block and is
@@ -54,15 +67,18 @@ __device__ __forceinline__ float ieee_op(float a, float b) {
 constexpr int kBlock = 32;            // sorted lookups per block (summation granule)
 constexpr int kTablesPerLaunch = 16;
 constexpr int kThreads = 256;
-constexpr int kPFJoin = 32;           // pieces loaded per batch in join
+constexpr int kPFJoin = 32;           // pieces per column in flight per batch of a join
+constexpr int kPFShort = 4;           // ... of a join of at most this many pieces
+constexpr int kSmallRows = 255;       // tables of at most this many rows go first in the block launch
 constexpr int64_t kMaxLookups = int64_t(1) << 24;
 constexpr int kSrcShift = 28;  // sorted values: source << 28 | batch row (batch < 2^28)
 
 // Workspace header (first 256 B of every sparse workspace).  The sort stage
-// stamps the fingerprint of the lookups it sorted; the block / join passes
-// compare it with their own call's before touching a table, and record a
+// stamps the fingerprint of the lookups it sorted; the block pass
+// compares it with its own call's before touching a table, and records a
 // mismatch (a presorted apply on another call's keys) or an out-of-call
-// (source, row) in `error` instead of applying anything from that block.
+// (source, row) in `error` instead of applying anything from that block (such a
+// block does not arrive at its segments' counters either: they stay unapplied).
 // tt_sparse_status() reads and clears `error`.
 constexpr uint32_t kHdrMagic = 0x54545350u;  // "TTSP"
 constexpr int kHdrBytes = 256;
@@ -103,6 +119,7 @@ struct Job {
   const uint32_t* keys;  // sorted
   const uint32_t* vals;  // sorted
   float* pieces;
+  uint32_t* arrived;     // per block of kBlock sorted lookups: pieces arrived of the segment starting there
   uint32_t* chunk_hist;  // chunked sort of small tables: digit counts [chunks][256]
   int32_t num_chunks;
   float* dense_out;      // kWriteSum: per-sorted-index segment sums [total][dim_max]
@@ -131,11 +148,18 @@ struct ApplyParams {
   float one_minus_beta2;
 };
 
+// the table whose wave range holds gw: the largest wave_begin <= gw (the ranges
+// are disjoint and start at 0, in an order make_plan chooses)
 __device__ __forceinline__ int table_of_wave(const Job& j, int gw) {
-  int t = 0;
+  int t = 0, best = -1;
 #pragma unroll 1
-  for (int i = 1; i < j.num; ++i)
-    if (gw >= j.t[i].wave_begin) t = i;
+  for (int i = 0; i < j.num; ++i) {
+    const int wb = j.t[i].wave_begin;
+    if (gw >= wb && wb > best) {
+      t = i;
+      best = wb;
+    }
+  }
   return t;
 }
 
@@ -162,6 +186,7 @@ __global__ void __launch_bounds__(kThreads) build_keys_kernel(const Job j, int t
   }
   j.keys_in[i] = (static_cast<uint32_t>(t) << j.id_bits) | id;
   j.vals_in[i] = val;
+  if (i % kBlock == 0) j.arrived[i / kBlock] = 0u;  // this call's join counters
   if (i == 0) {  // stamp the workspace with this call's fingerprint
     if (j.hdr->magic != kHdrMagic) {  // fresh workspace: no recorded error yet
       j.hdr->error = 0u;
@@ -353,6 +378,7 @@ __global__ void __launch_bounds__(kLsThreads) region_sort_kernel(const Job j) {
     n = T.n_pad;
   }
   const uint32_t nr = R.nr;
+  for (int e = tid; e < n / kBlock; e += kLsThreads) j.arrived[j.t[blockIdx.x].base / kBlock + e] = 0u;  // join counters
   if (blockIdx.x == 0 && tid == 0) {  // stamp the workspace with this call's fingerprint
     if (j.hdr->magic != kHdrMagic) {
       j.hdr->error = 0u;
@@ -540,6 +566,7 @@ __global__ void __launch_bounds__(kCsThreads) chunk_sort_kernel(const Job j) {
   const int n = min(kChunk, j.t[t].n_pad - c0);
   uint32_t* ck = j.keys_in + j.t[t].base + c0;  // chunk-sorted row keys
   uint32_t* cp = j.vals_in + j.t[t].base + c0;  // their region positions
+  if (tid < n / kBlock) j.arrived[(j.t[t].base + c0) / kBlock + tid] = 0u;  // this call's join counters
   if (blockIdx.x == 0 && tid == 0) {  // stamp the workspace with this call's fingerprint
     if (j.hdr->magic != kHdrMagic) {
       j.hdr->error = 0u;
@@ -760,20 +787,79 @@ __device__ __forceinline__ void store_row(const TableDesc& T, const ApplyParams&
   }
 }
 
-template <int OP>
-__device__ __forceinline__ void apply_row(const Job& j, const TableDesc& T, const ApplyParams& ap, uint32_t key,
-                                          int seg_start_sorted, int col, float g) {
-  const uint32_t id = key & ((1u << j.id_bits) - 1u);
-  if (OP == kWriteSum) {
-    j.dense_out[static_cast<int64_t>(seg_start_sorted) * j.dense_dim + col] = g;
-    return;
-  }
-  if (id >= static_cast<uint32_t>(T.num_rows)) return;  // invalid / padding
-  const int64_t o = static_cast<int64_t>(id) * T.dim + col;
-  store_row<OP>(T, ap, o, load_row<OP>(T, o), g);
+// Pieces pass between workgroups inside the launch.  They are stored
+// write-through and read past the caches (relaxed agent-scope atomics: sc1
+// stores and loads), so neither side needs a release of the L2 — which holds
+// this kernel's dirty table rows — or an invalidate; the store drain before
+// the counter add orders them.
+__device__ __forceinline__ void publish_piece(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float read_piece(const float* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// 3. per block of kBlock sorted lookups: piece sums; complete segments applied.
+// N pieces i0 .. i0 + N - 1 of two columns, all loads issued before the first
+// add (indices past piece n repeat piece n and are not added); piece 0 is the
+// first block's tail piece, the others are head pieces
+template <int N>
+__device__ __forceinline__ void add_pieces(const float* pcs, int dim, int i0, int n, int col, int col1, float& g0,
+                                           float& g1) {
+  float v0[N], v1[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const int i = min(i0 + q, n);
+    const float* p = pcs + static_cast<int64_t>(i) * 2 * dim + (i == 0 ? dim : 0);
+    v0[q] = read_piece(p + col);
+    v1[q] = read_piece(p + col1);
+  }
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const bool in = i0 + q <= n;
+    g0 = in ? ieee_op<'+'>(g0, v0[q]) : g0;
+    g1 = in ? ieee_op<'+'>(g1, v1[q]) : g1;
+  }
+}
+
+// 4. the join of one segment spanning blocks first .. last of table T, run by
+// the last block to arrive at its counter: 0 + the first block's tail piece,
+// then the head pieces of the following blocks in block order, then the
+// update of the row — the same chain whichever block runs it.  Two column
+// passes at a time; the row's state is loaded in the same round as the first
+// pieces, and kPFJoin pieces per column are in flight per batch (kPFShort for
+// the common segment of a few blocks).
+template <int OP>
+__device__ __forceinline__ void join_segment(const Job& j, const TableDesc& T, const ApplyParams& ap, uint32_t key,
+                                             int seg_start_sorted, int first, int last, int P, int li) {
+  const float* pcs = j.pieces + T.piece_off + static_cast<int64_t>(first) * 2 * T.dim;
+  const int dim = T.dim, n = last - first;  // pieces 0 .. n
+  const int64_t row = static_cast<int64_t>(key & ((1u << j.id_bits) - 1u)) * dim;  // a valid id: only those are joined
+  for (int col = li; col < dim; col += 2 * P) {
+    const bool two = col + P < dim;
+    const int col1 = two ? col + P : col;
+    RowState r0{0.0f, 0.0f}, r1{0.0f, 0.0f};
+    if (OP != kWriteSum) {
+      r0 = load_row<OP>(T, row + col);
+      r1 = load_row<OP>(T, row + col1);
+    }
+    float g0 = 0.0f, g1 = 0.0f;
+    if (n < kPFShort) {
+      add_pieces<kPFShort>(pcs, dim, 0, n, col, col1, g0, g1);
+    } else {
+      for (int i0 = 0; i0 <= n; i0 += kPFJoin) add_pieces<kPFJoin>(pcs, dim, i0, n, col, col1, g0, g1);
+    }
+    if (OP == kWriteSum) {
+      j.dense_out[static_cast<int64_t>(seg_start_sorted) * j.dense_dim + col] = g0;
+      if (two) j.dense_out[static_cast<int64_t>(seg_start_sorted) * j.dense_dim + col1] = g1;
+    } else {
+      store_row<OP>(T, ap, row + col, r0, g0);
+      if (two) store_row<OP>(T, ap, row + col1, r1, g1);
+    }
+  }
+}
+
+// 3. per block of kBlock sorted lookups: piece sums; complete segments applied;
+// 4. the last block to arrive at a longer segment's counter joins its pieces.
 template <int OP>
 __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const ApplyParams ap) {
   // wave-uniform (readfirstlane): the table descriptor is then read with scalar loads
@@ -786,7 +872,6 @@ __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const 
   const int nblk = T.n_pad / kBlock;
   if (blk >= nblk) return;
   const int b0 = T.base + blk * kBlock;   // first sorted index of the block
-  const int tend = T.base + T.n_pad;      // end of the table's region
   const uint32_t id_mask = (1u << j.id_bits) - 1u;
   uint32_t key[kBlock], off[kBlock];
 #pragma unroll
@@ -794,10 +879,23 @@ __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const 
     key[r] = j.keys[b0 + r];
     off[r] = j.vals[b0 + r];
   }
-  const uint32_t kprev = blk > 0 ? j.keys[b0 - 1] : ~0u;
-  const uint32_t knext = b0 + kBlock < tend ? j.keys[b0 + kBlock] : ~0u;
+  // In the same round of loads, the extent of the segments that leave and
+  // enter the block, in blocks: the segment of key[kBlock - 1] reaches block
+  // blk + 1 + i iff that block's first key equals it, the segment of key[0]
+  // reaches back to block blk - 1 - i iff that block's last key does (equal
+  // keys are contiguous; nothing else of the order is used).  Lane i of the
+  // slot's P probes both; the key holds on a prefix of the probes.
+  const int li = lane % P;
+  const uint64_t gmask = (P == kWave) ? ~0ull : (((1ull << P) - 1ull) << (lane - li));
+  const int nfwd = nblk - 1 - blk, nbwd = blk;  // blocks after / before this one
+  const uint32_t fk0 = j.keys[b0 + (li < nfwd ? kBlock * (1 + li) : 0)];
+  const uint32_t bk0 = j.keys[b0 - (li < nbwd ? 1 + kBlock * li : 0)];
   // the fingerprint check in the same round of loads as the keys
-  if (!keys_are_mine(j)) return;
+  const bool mine = keys_are_mine(j);
+  // blocks the two segments reach beyond this one, as far as the P probes see
+  int flo = __popcll(__ballot(li < nfwd && fk0 == key[kBlock - 1]) & gmask);
+  int blo = __popcll(__ballot(li < nbwd && bk0 == key[0]) & gmask);
+  if (!mine) return;
   // grad offsets (validated to fit 32 bits) and the segment structure; both are
   // the same for every column this lane visits.  The table's source offsets
   // are read ONCE into registers (indexing T.goff[] by a per-lane source made
@@ -823,8 +921,8 @@ __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const 
     atomicOr(&j.hdr->error, kErrOutOfCall);
     return;
   }
-  const bool head_cont = key[0] == kprev;
-  const bool tail_cont = key[kBlock - 1] == knext;
+  const bool head_cont = blo > 0;  // key[0] is the previous block's last key
+  const bool tail_cont = flo > 0;  // key[kBlock - 1] is the next block's first key
   {
     int seg_begin = 0;
 #pragma unroll
@@ -850,8 +948,8 @@ __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const 
       acc = ieee_op<'+'>(acc, v[r]);
       v[r] = acc;
       if (ends >> r & 1u) {
-        if (seg_begin == 0 && head_cont) pc[col] = acc;                    // piece of an earlier segment
-        else if (r == kBlock - 1 && tail_cont) pc[T.dim + col] = acc;      // first piece of a continuing one
+        if (seg_begin == 0 && head_cont) publish_piece(&pc[col], acc);                // piece of an earlier segment
+        else if (r == kBlock - 1 && tail_cont) publish_piece(&pc[T.dim + col], acc);  // first piece of a continuing one
         acc = 0.0f;
         seg_begin = r + 1;
       }
@@ -878,72 +976,61 @@ __global__ void __launch_bounds__(kThreads) block_sum_kernel(const Job j, const 
           store_row<OP>(T, ap, static_cast<int64_t>(key[r] & id_mask) * T.dim + col, st[r], ieee_op<'+'>(0.0f, v[r]));
     }
   }
-}
-
-// 4. segments spanning blocks: the block where one starts adds the pieces.
-template <int OP>
-__global__ void __launch_bounds__(kThreads) join_kernel(const Job j, const ApplyParams ap) {
-  // wave-uniform (readfirstlane): the table descriptor is then read with scalar loads
-  const int gw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave));
-  const int t = table_of_wave(j, gw);
-  const TableDesc& T = j.t[t];
-  const int P = T.lanes;
-  const int lane = lane_id();
-  const int blk = (gw - T.wave_begin) * (kWave / P) + lane / P;
-  const int nblk = T.n_pad / kBlock;
-  if (blk >= nblk) return;
-  const int b0 = T.base + blk * kBlock;
-  const int tend = T.base + T.n_pad;
-  // most blocks end no segment that continues: that test first, with the
-  // fingerprint check in the same round of loads
-  const uint32_t klast = j.keys[b0 + kBlock - 1];
-  const uint32_t knext = b0 + kBlock < tend ? j.keys[b0 + kBlock] : ~0u;
-  const bool mine = keys_are_mine(j);
-  if (!mine || knext != klast) return;
-  uint32_t key[kBlock];
-#pragma unroll
-  for (int r = 0; r < kBlock; ++r) key[r] = j.keys[b0 + r];
-  const uint32_t kprev = blk > 0 ? j.keys[b0 - 1] : ~0u;
-  // the invalid-id run (sorted last in the region) is never applied: skip its join
-  if ((klast & ((1u << j.id_bits) - 1u)) >= static_cast<uint32_t>(T.num_rows)) return;
-  // the continuing segment must START in this block
-  int seg_start = kBlock - 1;
-#pragma unroll
-  for (int r = kBlock - 2; r >= 0; --r)
-    if (key[r] == klast && seg_start == r + 1) seg_start = r;
-  if (seg_start == 0 && kprev == klast) return;  // began in an earlier block
-  // end of the segment: first sorted index in (b0+kBlock, tend) with a larger
-  // key, by a (P + 1)-ary search: the block's P lanes probe P evenly spaced
-  // positions per round (the keys equal klast on a prefix of them), so ~3
-  // dependent key loads at P = 64 instead of a binary search's ~14
-  int lo = b0 + kBlock, hi = tend;  // keys[lo] == klast, answer in (lo, hi]
-  {
-    const int li = lane % P, g0 = lane - li;  // lane in the block's group, the group's first lane
-    const uint64_t gmask = (P == kWave) ? ~0ull : (((1ull << P) - 1ull) << g0);
-    while (hi - lo > 1) {
-      const int step = (hi - lo + P) / (P + 1);  // ceil((hi - lo) / (P + 1)) >= 1
-      const int p = lo + (li + 1) * step;
-      const bool eq = p < hi && j.keys[p] == klast;
-      const int c = __popcll(__ballot(eq) & gmask);  // equal probes: lanes 0 .. c-1 of the group
-      const int nlo = lo + c * step;
-      if (c < P && lo + (c + 1) * step < hi) hi = lo + (c + 1) * step;
-      lo = nlo;
-    }
+  // 4. Hand-off of the pieces, last arriver joins; nobody waits.  Only valid
+  // segments are joined (the invalid-id run never is).  All of this is uniform
+  // over the P lanes of a block slot; the slots of a wave diverge.
+  const uint32_t rows = static_cast<uint32_t>(T.num_rows);
+  const uint32_t kf = key[kBlock - 1], kb = key[0];
+  const bool whole = ends == 1u << (kBlock - 1);              // one key fills the block
+  const bool head_seg = head_cont && (kb & id_mask) < rows;   // a segment enters the block
+  const bool fwd = tail_cont && (kf & id_mask) < rows;        // a segment leaves it
+  const bool tail_seg = fwd && !(whole && head_cont);         // ... and starts in it
+  if (!head_seg && !fwd) return;
+  // A segment that reaches past the P probed blocks (flo == P, blo == P): the
+  // rest of its extent by a (P + 1)-ary search over the remaining blocks, both
+  // directions in the same rounds.  [lo, hi): the key holds at probe lo - 1
+  // and at no probe >= hi.
+  int fhi = (fwd && flo == P) ? nfwd : flo, bhi = (head_seg && blo == P) ? nbwd : blo;
+  while (fhi > flo || bhi > blo) {
+    const int fs = (fhi - flo + P) / (P + 1) + (fhi == flo), bs = (bhi - blo + P) / (P + 1) + (bhi == blo);  // >= 1
+    const int fp = flo - 1 + (li + 1) * fs, bp = blo - 1 + (li + 1) * bs;  // fp >= flo: unknown probes only
+    const bool fin = fp < fhi, bin = bp < bhi;
+    const uint32_t fk = j.keys[b0 + (fin ? kBlock * (1 + fp) : 0)], bk = j.keys[b0 - (bin ? 1 + kBlock * bp : 0)];
+    const int fc = __popcll(__ballot(fin && fk == kf) & gmask);  // equal probes: lanes 0 .. c-1 of the slot
+    const int bc = __popcll(__ballot(bin && bk == kb) & gmask);
+    if (fc < P && flo + (fc + 1) * fs - 1 < fhi) fhi = flo + (fc + 1) * fs - 1;
+    if (bc < P && blo + (bc + 1) * bs - 1 < bhi) bhi = blo + (bc + 1) * bs - 1;
+    flo += fc * fs;
+    blo += bc * bs;
   }
-  const int last = (lo - T.base) / kBlock;  // last block holding the segment
-  const float* pcs = j.pieces + T.piece_off;
-  for (int col = lane % P; col < T.dim; col += P) {
-    float g = ieee_op<'+'>(0.0f, pcs[static_cast<int64_t>(blk) * 2 * T.dim + T.dim + col]);
-    for (int bb = blk + 1; bb <= last; bb += kPFJoin) {
-      float v[kPFJoin];
-#pragma unroll
-      for (int q = 0; q < kPFJoin; ++q)
-        v[q] = (bb + q <= last) ? pcs[static_cast<int64_t>(bb + q) * 2 * T.dim + col] : 0.0f;
-#pragma unroll
-      for (int q = 0; q < kPFJoin; ++q)
-        if (bb + q <= last) g = ieee_op<'+'>(g, v[q]);
+  const int last = blk + flo;    // last block of the leaving segment
+  const int first = blk - blo;   // first block of the entering segment
+  const int head_last = (whole && fwd) ? last : blk;
+  const int tail_start = kBlock - __clz(ends & ~(1u << (kBlock - 1)));  // first row of the block's last segment
+  // every piece this wave stored has reached memory before its tickets are drawn
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  uint32_t* arrived = j.arrived + T.base / kBlock;
+  uint32_t th = ~0u, tk = ~0u;  // both tickets in one round trip
+  if (li == 0 && head_seg) th = __hip_atomic_fetch_add(&arrived[first], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (li == 0 && tail_seg) tk = __hip_atomic_fetch_add(&arrived[blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // the ticket span - 1 is the last arriver's (~0u: no ticket drawn; a span is at most 2^19 blocks)
+  const bool join_head = (__ballot(th == static_cast<uint32_t>(head_last - first)) & gmask) != 0;
+  const bool join_tail = (__ballot(tk == static_cast<uint32_t>(last - blk)) & gmask) != 0;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the piece loads below the tickets
+#pragma unroll 1
+  for (int s = 0; s < 2; ++s) {
+    if (!(s == 0 ? join_head : join_tail)) continue;
+    const int f = s == 0 ? first : blk;
+    int start_sorted = b0 + tail_start;
+    if (OP == kWriteSum && s == 0) {  // the segment's first sorted index: the block's keys before it differ
+      int same = 0;
+      for (int r = li; r - li < kBlock; r += P)  // every lane of the slot takes every trip
+        same += __popcll(__ballot(r < kBlock && j.keys[T.base + f * kBlock + min(r, kBlock - 1)] == kb) & gmask);
+      start_sorted = T.base + (f + 1) * kBlock - same;
     }
-    apply_row<OP>(j, T, ap, klast, b0 + seg_start, col, g);
+    join_segment<OP>(j, T, ap, s == 0 ? kb : kf, start_sorted, f, s == 0 ? head_last : last, P, li);
+    // a repeated apply on the same sorted keys starts from zero again
+    if (li == 0) __hip_atomic_store(&arrived[f], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -1057,15 +1144,22 @@ int make_plan(const tt_sparse_table* tables, int cnt, int64_t batch, const float
     T.base = base;
     T.n_pad = static_cast<int32_t>(round_up(std::max<int64_t>(T.n, 1), kBlock));
     T.lanes = lanes_per_slot(s.dim);
-    T.wave_begin = waves;
     T.chunk_begin = chunks;
     T.piece_off = poff;
     base += T.n_pad;
     chunks += static_cast<int>(ceil_div(T.n_pad, kChunk));
-    const int nblk = T.n_pad / kBlock;
-    waves += static_cast<int>(ceil_div(nblk, kWave / T.lanes));
-    poff += static_cast<int64_t>(nblk) * 2 * s.dim;
+    poff += static_cast<int64_t>(T.n_pad / kBlock) * 2 * s.dim;
   }
+  // Wave order of the block launch: tables of at most kSmallRows rows first.
+  // Their blocks are nearly all pieces of long segments and load no row state,
+  // so their joins run under the large tables' row traffic, not after it.
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < cnt; ++i) {
+      TableDesc& T = j.t[i];
+      if ((T.num_rows <= kSmallRows) != (pass == 0)) continue;
+      T.wave_begin = waves;
+      waves += static_cast<int>(ceil_div(T.n_pad / kBlock, kWave / T.lanes));
+    }
   p->total = base;
   p->waves = waves;
   j.num_chunks = chunks;
@@ -1106,6 +1200,7 @@ struct PlanWs {
   SparseHeader* hdr;
   uint32_t *keys_in, *vals_in, *keys, *vals;
   float* pieces;
+  uint32_t* arrived;
   uint32_t* chunk_hist;
   float* dense_out;
   void* sort_tmp;
@@ -1118,6 +1213,7 @@ PlanWs carve_plan(Carver& cv, const Plan& p, int dense_dim) {
   w.keys = cv.take<uint32_t>(p.total);
   w.vals = cv.take<uint32_t>(p.total);
   w.pieces = cv.take<float>(std::max<int64_t>(p.piece_floats, 1));
+  w.arrived = cv.take<uint32_t>(p.total / kBlock);  // one join counter per block
   w.chunk_hist = cv.take<uint32_t>(static_cast<int64_t>(p.job.num_chunks) * 256);
   w.dense_out = dense_dim > 0 ? cv.take<float>(static_cast<int64_t>(p.total) * dense_dim) : nullptr;
   w.sort_tmp = cv.take<char>(static_cast<int64_t>(p.sort_bytes) + 256);
@@ -1173,8 +1269,9 @@ int sort_mode() {
 }
 
 // Stages: the key build + sort depends only on the ids, so a caller may run
-// it early on a side stream (kStageSort) and the gradient-dependent block/join
-// pass later (kStageApply) with the same tables, batch and workspace.
+// it early on a side stream (kStageSort) and the gradient-dependent block
+// launch (sums, joins, applies) later (kStageApply) with the same tables, batch
+// and workspace.
 enum SparseStage { kStageAll = 0, kStageSort = 1, kStageApply = 2 };
 
 template <int OP>
@@ -1200,6 +1297,7 @@ int run_sparse(const tt_sparse_table* tables, int32_t num_tables, int64_t batch,
     j.keys = w.keys;
     j.vals = w.vals;
     j.pieces = w.pieces;
+    j.arrived = w.arrived;
     j.chunk_hist = w.chunk_hist;
     j.dense_out = w.dense_out;
     j.dense_dim = dense_dim;
@@ -1240,8 +1338,6 @@ int run_sparse(const tt_sparse_table* tables, int32_t num_tables, int64_t batch,
     if (stage == kStageSort) continue;
     const int blocks = static_cast<int>(ceil_div(p.waves, kThreads / kWave));
     hipLaunchKernelGGL(block_sum_kernel<OP>, dim3(blocks), dim3(kThreads), 0, st, j, ap);
-    TT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(join_kernel<OP>, dim3(blocks), dim3(kThreads), 0, st, j, ap);
     TT_CHECK_LAUNCH();
     if (OP == kWriteSum) {
       hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, j, out_uniq, out_sum, out_count);
@@ -1435,7 +1531,7 @@ __global__ void __launch_bounds__(kRoutedThreads) routed_keys_kernel(const Job j
     // -1 - owner: its lookups keep their place in the (owner, tag) group and
     // take the invalid key with no gradient (like an out-of-range id: never
     // applied, never written — an invalid run may sit mid-region; block_sum
-    // and join only need equal keys contiguous)
+    // and its join only need equal keys contiguous)
     const int s = r.slot[lk];
     const int o = s >= 0 ? static_cast<int>(s / r.cap) : -1 - s;
     const int g = o * T + r.lk_tag[l];
@@ -1459,6 +1555,7 @@ __global__ void __launch_bounds__(kRoutedThreads) routed_keys_kernel(const Job j
       const_cast<uint32_t*>(j.vals)[dst] = 0xFFFFFFFFu;
     }
   }
+  if (i < r.total + r.pad_begin[r.num_tables] && i % kBlock == 0) j.arrived[i / kBlock] = 0u;  // join counters
   if (i == 0) {  // stamp the workspace with this call's fingerprint
     if (j.hdr->magic != kHdrMagic) {
       j.hdr->error = 0u;
@@ -1771,6 +1868,7 @@ extern "C" int tt_sparse_routed(const tt_sparse_table* tables, int32_t num_table
   Job& j = p.job;
   j.keys = w.keys;
   j.vals = w.vals;
+  j.arrived = w.arrived;
   j.hdr = w.hdr;
   RoutedArgs a{};
   a.order = rs->order;

@@ -271,9 +271,13 @@ int tt_sparse_adagrad(const tt_sparse_table* tables, int32_t num_tables,
 /* The same update in two stages.  tt_sparse_sort builds and sorts the
  * (table | row id, lookup) keys — it reads only the ids, so it can run early
  * on a side stream, overlapped with the forward/backward compute;
- * tt_sparse_adagrad_sorted then does the segmented sums and the apply.  Both
- * calls must see the same tables (<= 16), batch and workspace, in that order.
- * Results are identical to tt_sparse_adagrad. */
+ * tt_sparse_adagrad_sorted then does the segmented sums and the apply in ONE
+ * launch: a segment longer than a 32-lookup block is joined inside it by the
+ * last of its blocks to arrive at the segment's counter (one counter per
+ * block in the workspace, zeroed by the sort stage and again by the joiner,
+ * so the apply may be repeated on one sort); no block waits for another.
+ * Both calls must see the same tables (<= 16), batch and workspace, in that
+ * order.  Results are identical to tt_sparse_adagrad. */
 int tt_sparse_sort(const tt_sparse_table* tables, int32_t num_tables,
                    int64_t batch, void* workspace, size_t workspace_bytes,
                    tt_stream_t stream);
@@ -295,11 +299,11 @@ int tt_sparse_adagrad_rows(const tt_sparse_table* tables, int32_t num_tables,
 
 /* The sparse calls never fault on a mismatched workspace: the sort stage
  * stamps the first 256 bytes of the workspace with a fingerprint of the
- * lookups it sorted, and the apply passes (of every sparse entry point above
- * and below) check it before touching a table.  A presorted apply that finds
+ * lookups it sorted, and the apply launch (of every sparse entry point above
+ * and below) checks it before touching a table.  A presorted apply that finds
  * another call's keys (or a sorted lookup pointing outside the call's
- * gradient) applies nothing from the affected blocks and records the error
- * in the header.  tt_sparse_status synchronises `stream`, returns
+ * gradient) applies nothing from the affected blocks (nor from a longer
+ * segment they hold a piece of) and records the error in the header.  tt_sparse_status synchronises `stream`, returns
  * TT_ERR_BAD_ARG (message in tt_last_error) if an error was recorded since
  * the last check, and clears it.  A fresh workspace should start zeroed. */
 int tt_sparse_status(void* workspace, size_t workspace_bytes, tt_stream_t stream);
@@ -355,7 +359,7 @@ int tt_sparse_routed(const tt_sparse_table* tables, int32_t num_tables, int64_t 
                      int32_t op, float lr, float epsilon, void* workspace,
                      size_t workspace_bytes, tt_stream_t stream);
 
-/* tt_sparse_scatter_sum's block / join passes on keys tt_sparse_sort sorted
+/* tt_sparse_scatter_sum's block launch (sums and joins) on keys tt_sparse_sort sorted
  * earlier (same tables, batch and workspace; the sort reads only the ids and
  * accepts tables without slots): the sort can run beside other work. */
 int tt_sparse_scatter_sum_sorted(const tt_sparse_table* tables, int32_t num_tables,
