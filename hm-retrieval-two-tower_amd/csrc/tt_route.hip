@@ -28,6 +28,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "tt_common.h"
+#include "tt_wg_sort.h"
 
 namespace tt {
 namespace {
@@ -235,13 +236,10 @@ __global__ void __launch_bounds__(256) route_owner_kernel(const int32_t* recv, i
 // start offsets in LDS from the device counts (world <= kMaxWorld), then one
 // thread per padded slot copies its request (or writes the (-1, -1) filler)
 // and one thread per lookup rewrites its request index to the padded slot.
-// own_tags / own_rows / own_tids (optional, world 1): tt_route_owner's view
-// of the slots written in the same pass.
 __global__ void __launch_bounds__(256) route_pad_kernel(const int32_t* send, const long long* counts,
                                                         const int32_t* idx, int64_t num_lookups, int32_t world,
                                                         int64_t cap, int32_t* send_padded, int32_t* idx_padded,
-                                                        int32_t* overflow, int32_t num_tags, int32_t* own_tags,
-                                                        int32_t* own_rows, int32_t* own_tids) {
+                                                        int32_t* overflow) {
   __shared__ long long start[kMaxWorld + 1];
   if (threadIdx.x == 0) {
     long long run = 0;
@@ -266,11 +264,6 @@ __global__ void __launch_bounds__(256) route_pad_kernel(const int32_t* send, con
     }
     send_padded[2 * t] = row;
     send_padded[2 * t + 1] = tag;
-    if (own_tags) {  // world 1: the local row is the row
-      own_tags[t] = tag;
-      own_rows[t] = row;
-      for (int q = 0; q < num_tags; ++q) own_tids[static_cast<int64_t>(q) * slots + t] = q == tag ? row : -1;
-    }
     if (j == cap - 1 && n > cap && overflow) atomicAdd(overflow, static_cast<int32_t>(n - cap));
   }
   if (t < num_lookups) {
@@ -314,8 +307,8 @@ constexpr int kRsWaves = kRsThreads / kWave;
 constexpr int kRsMax = 8192;
 constexpr int kRsPer = kRsMax / kRsThreads;  // lookups staged per thread
 constexpr int kRsTiles = kRsMax / kRsWaves / kWave;  // 64-lane tiles per wave at the maximum
-constexpr int kRsHistStride = kRsWaves + 1;
-constexpr size_t kRsLdsBytes = size_t(kRsMax) * 4 + size_t(2) * kRsMax * 2 + size_t(256) * kRsHistStride * 4 +
+using RsHist = DigitHist<kRsWaves>;
+constexpr size_t kRsLdsBytes = size_t(kRsMax) * 4 + size_t(2) * kRsMax * 2 + size_t(RsHist::kWords) * 4 +
                                size_t(2) * (kMaxWorld + 1) * 4;
 
 struct RouteFixedArgs {
@@ -336,56 +329,17 @@ struct RouteFixedArgs {
   int32_t* own_tids;
 };
 
-// lanes of this wave holding the same digit among the active lanes (one
-// ballot per digit bit, nbits <= 8, wave-uniform)
-__device__ __forceinline__ uint64_t rs_peers(uint32_t d, bool act, int nbits) {
-  const uint64_t a = __ballot(act);
-  uint32_t lo = static_cast<uint32_t>(a), hi = static_cast<uint32_t>(a >> 32);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    if (b >= nbits) break;
-    const uint32_t bit = (d >> b) & 1u;
-    const uint64_t bal = __ballot(bit);
-    const uint32_t flip = bit - 1u;
-    lo &= static_cast<uint32_t>(bal) ^ flip;
-    hi &= static_cast<uint32_t>(bal >> 32) ^ flip;
-  }
-  return act ? (static_cast<uint64_t>(hi) << 32 | lo) : 0;
-}
-
-// block-wide exclusive scan of one int per thread; *total = the sum
-__device__ __forceinline__ int rs_scan(int v, int* wsum, int* total) {
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int y = __shfl_up(x, o, kWave);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();  // wsum free (an earlier scan's readers are done)
-  if (lane == kWave - 1) wsum[w] = x;
-  __syncthreads();
-  int ex = x - v, t = 0;
-  for (int q = 0; q < kRsWaves; ++q) {
-    const int c = wsum[q];
-    ex += q < w ? c : 0;
-    t += c;
-  }
-  *total = t;
-  return ex;
-}
-
 __global__ void __launch_bounds__(kRsThreads) route_fixed_small_kernel(const RouteFixedArgs a) {
   extern __shared__ __attribute__((aligned(16))) char rsm[];
   uint32_t* lkey = reinterpret_cast<uint32_t*>(rsm);
   uint16_t* pb0 = reinterpret_cast<uint16_t*>(rsm + kRsMax * 4);
   uint16_t* pb1 = pb0 + kRsMax;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(rsm + kRsMax * 8);  // [256][kRsHistStride]
-  int* cnt = reinterpret_cast<int*>(rsm + kRsMax * 8 + 256 * kRsHistStride * 4);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(rsm + kRsMax * 8);  // [256][RsHist::kStride]
+  int* cnt = reinterpret_cast<int*>(rsm + kRsMax * 8 + RsHist::kWords * 4);
   int* start = cnt + (kMaxWorld + 1);
   __shared__ int wsum[kRsWaves];
   TT_RS_STAMP(5)
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
+  const int tid = threadIdx.x;
   const int n = static_cast<int>(a.batch * a.num);
   const int W = a.world, T = a.num_tags;
   // keys: (owner, tag, row + 1) as in route_keys_kernel, 32 bits; every id
@@ -421,71 +375,22 @@ __global__ void __launch_bounds__(kRsThreads) route_fixed_small_kernel(const Rou
       a.grp_last[g] = -1;
     }
   TT_RS_STAMP(0)
-  // stable LSD radix sort of the positions by key
-  const int per = ((n + kRsWaves - 1) / kRsWaves + kWave - 1) / kWave * kWave;
-  const int wbeg = w * per, wend = min(n, wbeg + per);
-  const uint64_t lt = (uint64_t(1) << lane) - 1u;
+  // stable LSD radix sort of the positions by key (tt_wg_sort.h); the sorted
+  // order stays in LDS (src) for the request scan
+  const WaveSlice<kRsWaves> s(n);
   const int passes = (a.end_bit + 7) / 8;
   const int width = (a.end_bit + passes - 1) / passes;
   const uint32_t dmask = (1u << width) - 1u;
   uint16_t* src = pb0;
   uint16_t* dst = pb1;
   for (int p = 0; p < passes; ++p) {
-    const int sh = p * width;
-    for (int e = tid; e < 256 * kRsHistStride; e += kRsThreads) hist[e] = 0u;
+    RsHist::clear(hist);
     __syncthreads();
-    uint16_t pos[kRsTiles];
-    uint32_t dig[kRsTiles];
-    uint64_t peer[kRsTiles];
-#pragma unroll
-    for (int q = 0; q < kRsTiles; ++q) {
-      const int i = wbeg + q * kWave + lane;
-      pos[q] = 0;
-      dig[q] = 0;
-      if (i < wend) {
-        pos[q] = src[i];
-        dig[q] = (lkey[pos[q]] >> sh) & dmask;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kRsTiles; ++q) {
-      peer[q] = 0;
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        peer[q] = rs_peers(dig[q], wbeg + q * kWave + lane < wend, width);
-        if (peer[q] != 0 && __builtin_ctzll(peer[q]) == lane) hist[dig[q] * kRsHistStride + w] += __popcll(peer[q]);
-      }
-    }
-    __syncthreads();
-    {  // counts -> exclusive offsets in (digit, wave) order: 4 words per thread
-      uint32_t h[4], run = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int L = 4 * tid + u;
-        h[u] = hist[(L / kRsWaves) * kRsHistStride + L % kRsWaves];
-        run += h[u];
-      }
-      int tot;
-      uint32_t ex = static_cast<uint32_t>(rs_scan(static_cast<int>(run), wsum, &tot));
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int L = 4 * tid + u;
-        hist[(L / kRsWaves) * kRsHistStride + L % kRsWaves] = ex;
-        ex += h[u];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kRsTiles; ++q) {
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        const uint64_t m = peer[q];
-        if (m != 0) {
-          uint32_t* slot = &hist[dig[q] * kRsHistStride + w];
-          const uint32_t off = *slot;
-          dst[off + __popcll(m & lt)] = pos[q];
-          if (__builtin_ctzll(m) == lane) *slot = off + __popcll(m);
-        }
-      }
-    }
+    LsdPass<kRsWaves, kRsTiles> pass;
+    pass.load(s, src, lkey, p * width, dmask);
+    pass.count(s, hist, width);
+    RsHist::scan(hist, reinterpret_cast<uint32_t*>(wsum));
+    pass.scatter(s, hist, [&](uint32_t o, uint16_t ps) { dst[o] = ps; });
     __syncthreads();
     uint16_t* t = src;
     src = dst;
@@ -517,11 +422,11 @@ __global__ void __launch_bounds__(kRsThreads) route_fixed_small_kernel(const Rou
   }
   if (run_n) atomicAdd(&cnt[run_owner], run_n);
   int nreq;
-  const int ubase = rs_scan(heads, wsum, &nreq);
+  const int ubase = wg_exclusive_scan<kRsWaves>(heads, wsum, &nreq);
   {  // owners' first request: exclusive scan of cnt (W <= kRsThreads)
     int tot;
     const int c = tid < W ? cnt[tid] : 0;
-    const int ex = rs_scan(c, wsum, &tot);
+    const int ex = wg_exclusive_scan<kRsWaves>(c, wsum, &tot);
     if (tid < W) start[tid] = ex;
   }
   __syncthreads();
@@ -778,8 +683,7 @@ extern "C" int tt_route_pad(const int32_t* send, const long long* counts, const 
   TT_REQUIRE(static_cast<int64_t>(world) * cap < (int64_t(1) << 31), "tt_route_pad: world * cap exceeds int32");
   const int64_t n = std::max<int64_t>(static_cast<int64_t>(world) * cap, num_lookups);
   hipLaunchKernelGGL(route_pad_kernel, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, to_stream(stream),
-                     send, counts, idx, num_lookups, world, cap, send_padded, idx_padded, overflow, 1, nullptr,
-                     nullptr, nullptr);
+                     send, counts, idx, num_lookups, world, cap, send_padded, idx_padded, overflow);
   TT_CHECK_LAUNCH();
   return TT_OK;
 }
@@ -801,13 +705,6 @@ FixedWs carve_fixed(Carver& cv, const RoutePlan& p) {
   f.idx = cv.take<int32_t>(p.total);
   f.nreq = cv.take<int32_t>(1);
   return f;
-}
-bool route_w1_slots() {  // TT_ROUTE_W1_SLOTS=0: world 1 through route_pad as well (A/B)
-  static const bool off = [] {
-    const char* e = std::getenv("TT_ROUTE_W1_SLOTS");
-    return e && e[0] == '0';
-  }();
-  return !off;
 }
 bool route_fused(const RoutePlan& p) {
   static const bool off = [] {
@@ -880,7 +777,7 @@ extern "C" int tt_route_fixed(const tt_route_lookup* lookups, int32_t num_lookup
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "tt_route_fixed: workspace %zu < required %zu", workspace_bytes, cv.used());
   const size_t rbytes = static_cast<size_t>(reinterpret_cast<char*>(f.send) - static_cast<char*>(workspace));
-  if (world == 1 && route_w1_slots()) {
+  if (world == 1) {
     // one owner: the head / write passes lay the slots out themselves
     const World1Slots w1{cap, send_padded, idx_padded, overflow, owner_tags, owner_rows, owner_table_ids, num_tags};
     return route_requests(lookups, num_lookups, batch, world, num_tags, f.send, counts, f.nreq, f.idx, order,
@@ -889,11 +786,10 @@ extern "C" int tt_route_fixed(const tt_route_lookup* lookups, int32_t num_lookup
   rc = route_requests(lookups, num_lookups, batch, world, num_tags, f.send, counts, f.nreq, f.idx, order, grp_first,
                       grp_last, workspace, rbytes, stream, World1Slots{});
   if (rc) return rc;
-  // tt_route_pad, with the world-1 owner view written by the same pass
+  // tt_route_pad (no owner view: that is the world-1 shortcut above)
   const int64_t n = std::max<int64_t>(static_cast<int64_t>(world) * cap, p.total);
   hipLaunchKernelGGL(route_pad_kernel, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, f.send,
-                     counts, f.idx, p.total, world, cap, send_padded, idx_padded, overflow, num_tags, owner_tags,
-                     owner_rows, owner_table_ids);
+                     counts, f.idx, p.total, world, cap, send_padded, idx_padded, overflow);
   TT_CHECK_LAUNCH();
   return TT_OK;
 }

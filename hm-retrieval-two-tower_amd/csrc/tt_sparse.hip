@@ -14,10 +14,17 @@
 //     row id) with the lookup index as value, each table's region padded to a
 //     multiple of kBlock with an "invalid" id that sorts last, sorted stably so
 //     each table's lookups come out grouped by row id in increasing batch
-//     position.  Default: ONE launch, one workgroup per table sorting its
-//     region in LDS (region_sort_kernel; regions of <= 16384 lookups, or any
-//     size for tables of <= 255 rows).  Otherwise (or TT_SPARSE_SORT=device):
-//     a key-build launch + one rocPRIM radix sort over the key bits in use.
+//     position.  Three paths, chosen by size alone (run_sparse):
+//     chunked — every region cut into chunks of 2048 lookups, each sorted in
+//       LDS by its own workgroup (chunk_sort_kernel), then merged
+//       (chunk_merge_kernel): two launches.  Taken when every region fits the
+//       merge: <= 131072 lookups for tables of <= 255 rows, <= 32768 otherwise.
+//       The train step's tables all do.
+//     small tables — else, when every table of the call has <= 255 rows: one
+//       launch, one workgroup per table doing one counting pass on the whole
+//       row id (small_table_sort_kernel; any region size).
+//     device — else: a key-build launch + one rocPRIM radix sort over the key
+//       bits in use.
 //  3. blocks — one (sub-)wave per kBlock consecutive sorted lookups of a
 //     table, lanes over embedding columns (coalesced row reads): sequential
 //     fp32 sums of each segment piece; a segment that starts and ends inside
@@ -47,11 +54,10 @@
 // rounded fp32 divide/sqrt) so results match the CPU restatement bit for bit.
 // (HIP's __fsqrt_rn maps to the approximate native sqrt on this toolchain.)
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "tt_common.h"
+#include "tt_wg_sort.h"
 
 namespace tt {
 namespace {
@@ -139,6 +145,17 @@ __device__ __forceinline__ bool keys_are_mine(const Job& j) {
   return false;
 }
 
+// The sort stage's stamp: the workspace carries this call's fingerprint (one
+// thread of the launch).
+__device__ __forceinline__ void stamp_header(const Job& j) {
+  if (j.hdr->magic != kHdrMagic) {  // fresh workspace: no recorded error yet
+    j.hdr->error = 0u;
+    j.hdr->magic = kHdrMagic;
+  }
+  j.hdr->fp0 = j.fp0;
+  j.hdr->fp1 = j.fp1;
+}
+
 enum ApplyOp { kWriteSum = 0, kAdagrad = 1, kAdamScatter = 2, kScatterSum = 3 };
 
 struct ApplyParams {
@@ -187,38 +204,16 @@ __global__ void __launch_bounds__(kThreads) build_keys_kernel(const Job j, int t
   j.keys_in[i] = (static_cast<uint32_t>(t) << j.id_bits) | id;
   j.vals_in[i] = val;
   if (i % kBlock == 0) j.arrived[i / kBlock] = 0u;  // this call's join counters
-  if (i == 0) {  // stamp the workspace with this call's fingerprint
-    if (j.hdr->magic != kHdrMagic) {  // fresh workspace: no recorded error yet
-      j.hdr->error = 0u;
-      j.hdr->magic = kHdrMagic;
-    }
-    j.hdr->fp0 = j.fp0;
-    j.hdr->fp1 = j.fp1;
-  }
+  if (i == 0) stamp_header(j);
 }
 
-// 1+2 fused for regions of at most kLdsSortMax lookups: one workgroup per
-// table builds its region's keys straight into LDS and sorts them there by a
-// stable LSD radix sort over the bits the table's row ids use (8-bit digits at
-// most), then writes the same sorted (key, value) arrays the rocPRIM path
-// writes.  The table index is the key's high part and each table owns its
-// region, so sorting the regions one by one equals the global sort.  One
-// launch on one CU per table instead of a key build and a multi-launch device
-// sort: it runs beside the backward without taking the chip.
-//   LDS: row key per original position (u32), position ping-pong (u16) and the
-//   per-wave digit counts [digit][wave].  Each wave owns a contiguous slice of
-//   the current order; ranks inside a 64-lane tile come from 8 ballots (lanes
-//   with equal digits), so the scatter keeps the order: stable.
-constexpr int kLdsSortMax = 16384;
-constexpr int kLsThreads = 1024;
-constexpr int kLsWaves = kLsThreads / kWave;
-constexpr int kLsTiles = kLdsSortMax / kLsWaves / kWave;  // 64-lane tiles per wave at the maximum
-// digit counts [256 digits][kLsWaves] at a row stride of kLsWaves + 1 words, so
-// the distinct digits of one wave's lanes fall in distinct LDS banks
-constexpr int kHistStride = kLsWaves + 1;
-constexpr int kLsLdsBytes = kLdsSortMax * 4 + 2 * kLdsSortMax * 2 + 256 * kHistStride * 4;
+// 1+2 fused in LDS (the small-table and chunked sorts below): workgroups build
+// their region's row keys from the ids and sort them by the pieces of
+// tt_wg_sort.h over the bits the table's row ids use (8-bit digits at most),
+// then write the same sorted (key, value) arrays the rocPRIM path writes.  The
+// table index is the key's high part and each table owns its region, so
+// sorting the regions one by one equals the global sort.
 
-// row key of region position i: the row id, or nr for invalid ids and padding
 // One region's descriptor in registers (a reference into the kernel's
 // by-value Job indexed by blockIdx.x made the compiler copy the whole Job to
 // scratch).
@@ -232,6 +227,23 @@ struct Region {
   uint32_t khi;    // table index << id_bits
   uint32_t invalid;
 };
+
+__device__ __forceinline__ Region region_of(const Job& j, int t) {
+  const TableDesc& T = j.t[t];
+  Region R;
+  R.ids0 = T.ids[0];
+  R.ids1 = T.ids[1];
+  R.ids2 = T.ids[2];
+  R.ids3 = T.ids[3];
+  R.batch = j.batch;
+  R.keys = const_cast<uint32_t*>(j.keys) + T.base;
+  R.vals = const_cast<uint32_t*>(j.vals) + T.base;
+  R.n = T.n;
+  R.nr = static_cast<uint32_t>(T.num_rows);
+  R.khi = static_cast<uint32_t>(t) << j.id_bits;
+  R.invalid = (1u << j.id_bits) - 1u;
+  return R;
+}
 
 __device__ __forceinline__ int source_of(const Region& R, int64_t i) {  // i / batch for i < 4 * batch
   return (i >= R.batch) + (i >= 2 * R.batch) + (i >= 3 * R.batch);
@@ -253,37 +265,48 @@ __device__ __forceinline__ uint32_t region_key(const Region& R, int i) {
   return (valid && r >= 0 && static_cast<uint32_t>(r) < R.nr) ? static_cast<uint32_t>(r) : R.nr;
 }
 
+// Small-table sort: one 1024-thread workgroup per table of at most 255 rows
+// (row keys of <= 8 bits, host-checked) sorts its whole region, of any size,
+// by ONE counting pass on the row key.  Run when a call is all such tables and
+// one of them is too long for the chunked sort's merge: one launch on one CU
+// per table instead of a key build and a multi-launch device sort.
+//   LDS: the per-wave digit counts [digit][wave], then the region's row keys
+//   as bytes for the regions that fit kStStageMax (dynamic, sized by the host
+//   to the longest such region of the call); a longer region re-reads its ids.
+constexpr int kStThreads = 1024;
+constexpr int kStWaves = kStThreads / kWave;
+constexpr int kStStageMax = 131072;  // most row keys staged in LDS (bytes)
+using StHist = DigitHist<kStWaves>;
+
 // row keys of one source's positions [s*batch, (s+1)*batch) into LDS, 16
 // independent id loads in flight per thread (the source's pointer is uniform
 // and written out per call: a select among the four made the compiler index
 // them from scratch)
-template <typename KT>
-__device__ __forceinline__ void stage_source(const Region& R, const int32_t* __restrict__ ids, int s, KT* dst) {
+__device__ __forceinline__ void stage_source(const Region& R, const int32_t* __restrict__ ids, int s, uint8_t* dst) {
   const int nb = static_cast<int>(R.batch);
-  for (int base = 0; base < nb; base += 16 * kLsThreads) {
+  for (int base = 0; base < nb; base += 16 * kStThreads) {
     int32_t r[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-      const int b = base + u * kLsThreads + static_cast<int>(threadIdx.x);
+      const int b = base + u * kStThreads + static_cast<int>(threadIdx.x);
       r[u] = ids[b < nb ? b : 0];
     }
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-      const int b = base + u * kLsThreads + static_cast<int>(threadIdx.x);
+      const int b = base + u * kStThreads + static_cast<int>(threadIdx.x);
       const uint32_t k = (r[u] >= 0 && static_cast<uint32_t>(r[u]) < R.nr) ? static_cast<uint32_t>(r[u]) : R.nr;
-      if (b < nb) dst[s * nb + b] = static_cast<KT>(k);
+      if (b < nb) dst[s * nb + b] = static_cast<uint8_t>(k);
     }
   }
 }
 
 // row keys of positions [0, n) into LDS (padding past the lookups: nr)
-template <typename KT>
-__device__ __forceinline__ void stage_keys(const Region& R, int n, KT* dst) {
+__device__ __forceinline__ void stage_keys(const Region& R, int n, uint8_t* dst) {
   stage_source(R, R.ids0, 0, dst);
   if (R.n > R.batch) stage_source(R, R.ids1, 1, dst);
   if (R.n > 2 * R.batch) stage_source(R, R.ids2, 2, dst);
   if (R.n > 3 * R.batch) stage_source(R, R.ids3, 3, dst);
-  for (int i = R.n + static_cast<int>(threadIdx.x); i < n; i += kLsThreads) dst[i] = static_cast<KT>(R.nr);
+  for (int i = R.n + static_cast<int>(threadIdx.x); i < n; i += kStThreads) dst[i] = static_cast<uint8_t>(R.nr);
 }
 
 // sorted (key, value) at output slot `out` of region position ps with row key k
@@ -297,182 +320,38 @@ __device__ __forceinline__ void region_store(const Region& R, int out, uint32_t 
   R.vals[out] = val;
 }
 
-// lanes of this wave holding the same digit (among the `act` lanes): one
-// ballot per digit bit (d < 2^nbits, nbits <= 8, wave-uniform), each lane
-// keeping the lanes that agree with its bit
-__device__ __forceinline__ uint64_t digit_peers(uint32_t d, bool act, int nbits) {
-  const uint64_t a = __ballot(act);
-  uint32_t lo = static_cast<uint32_t>(a), hi = static_cast<uint32_t>(a >> 32);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    if (b >= nbits) break;
-    const uint32_t bit = (d >> b) & 1u;
-    const uint64_t bal = __ballot(bit);
-    const uint32_t flip = bit - 1u;  // 0 when the bit is set, all ones when clear
-    lo &= static_cast<uint32_t>(bal) ^ flip;
-    hi &= static_cast<uint32_t>(bal >> 32) ^ flip;
-  }
-  return act ? (static_cast<uint64_t>(hi) << 32 | lo) : 0;
-}
-
-// word of (digit, wave) entry L = digit * kLsWaves + wave of the padded histogram
-__device__ __forceinline__ int hist_word(int L) { return (L / kLsWaves) * kHistStride + L % kLsWaves; }
-
-// one wave's count of a tile: the lowest lane of each digit adds its peers
-// (distinct digits, distinct words; the wave's own tiles run in order)
-__device__ __forceinline__ void count_peers(uint32_t* hist, uint32_t d, uint64_t m, int w) {
-  if (m != 0 && __builtin_ctzll(m) == static_cast<int>(lane_id())) hist[d * kHistStride + w] += __builtin_popcountll(m);
-}
-
-// hist[digit][wave] counts -> exclusive offsets in (digit, wave) order
-__device__ __forceinline__ void scan_digit_counts(uint32_t* hist, uint32_t* wsum) {
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
-  __syncthreads();
-  uint32_t h[4], run = 0;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    h[u] = hist[hist_word(4 * tid + u)];
-    run += h[u];
-  }
-  uint32_t inc = run;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o, kWave);
-    if (lane >= o) inc += y;
-  }
-  if (lane == kWave - 1) wsum[w] = inc;
-  __syncthreads();
-  uint32_t ex = inc - run;
-  for (int v = 0; v < w; ++v) ex += wsum[v];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    hist[hist_word(4 * tid + u)] = ex;
-    ex += h[u];
-  }
-  __syncthreads();
-}
-
-__global__ void __launch_bounds__(kLsThreads) region_sort_kernel(const Job j) {
+__global__ void __launch_bounds__(kStThreads) small_table_sort_kernel(const Job j) {
   extern __shared__ __attribute__((aligned(16))) char lsm[];
-  uint32_t* lkey = reinterpret_cast<uint32_t*>(lsm);
-  uint16_t* const pbuf0 = reinterpret_cast<uint16_t*>(lsm + kLdsSortMax * 4);
-  uint16_t* const pbuf1 = pbuf0 + kLdsSortMax;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(lsm + kLdsSortMax * 8);  // [256 digits][kHistStride]
-  __shared__ uint32_t wsum[kLsWaves];
+  uint32_t* hist = reinterpret_cast<uint32_t*>(lsm);  // [256 digits][StHist::kStride]
+  uint8_t* k8 = reinterpret_cast<uint8_t*>(lsm + StHist::kWords * 4);
+  __shared__ uint32_t wsum[kStWaves];
   const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
-  Region R;
-  int n;
-  {
-    const TableDesc& T = j.t[blockIdx.x];
-    R.ids0 = T.ids[0];
-    R.ids1 = T.ids[1];
-    R.ids2 = T.ids[2];
-    R.ids3 = T.ids[3];
-    R.batch = j.batch;
-    R.keys = const_cast<uint32_t*>(j.keys) + T.base;
-    R.vals = const_cast<uint32_t*>(j.vals) + T.base;
-    R.n = T.n;
-    R.nr = static_cast<uint32_t>(T.num_rows);
-    R.khi = static_cast<uint32_t>(blockIdx.x) << j.id_bits;
-    R.invalid = (1u << j.id_bits) - 1u;
-    n = T.n_pad;
+  const int t = blockIdx.x;
+  const Region R = region_of(j, t);
+  const int n = j.t[t].n_pad;
+  for (int e = tid; e < n / kBlock; e += kStThreads) j.arrived[j.t[t].base / kBlock + e] = 0u;  // join counters
+  if (t == 0 && tid == 0) stamp_header(j);
+  const int bits = 32 - __builtin_clz(R.nr);  // row keys lie in [0, nr]: <= 8 bits
+  const WaveSlice<kStWaves> s(n);
+  StHist::clear(hist);
+  // the keys are staged in LDS as bytes when they fit, else re-read from the ids
+  const bool staged = n <= kStStageMax;
+  if (staged) stage_keys(R, n, k8);
+  __syncthreads();
+  for (int t0 = s.beg; t0 < s.end; t0 += kWave) {  // counts: peers per tile, no LDS atomics
+    const int i = t0 + lane;
+    const bool act = i < s.end;
+    const uint32_t d = act ? (staged ? k8[i] : region_key(R, i)) : 0u;
+    StHist::count(hist, d, digit_peers(d, act, bits), w);
   }
-  const uint32_t nr = R.nr;
-  for (int e = tid; e < n / kBlock; e += kLsThreads) j.arrived[j.t[blockIdx.x].base / kBlock + e] = 0u;  // join counters
-  if (blockIdx.x == 0 && tid == 0) {  // stamp the workspace with this call's fingerprint
-    if (j.hdr->magic != kHdrMagic) {
-      j.hdr->error = 0u;
-      j.hdr->magic = kHdrMagic;
-    }
-    j.hdr->fp0 = j.fp0;
-    j.hdr->fp1 = j.fp1;
-  }
-  const int bits = 32 - __builtin_clz(nr);  // row keys lie in [0, nr]
-  const int per = ((n + kLsWaves - 1) / kLsWaves + kWave - 1) / kWave * kWave;
-  const int wbeg = w * per, wend = min(n, wbeg + per);
-  const uint64_t lt = (uint64_t(1) << lane) - 1u;
-  for (int e = tid; e < 256 * kHistStride; e += kLsThreads) hist[e] = 0u;
-  if (bits <= 8) {
-    // small table: ONE counting pass on the whole key (any region size); the
-    // keys are staged in LDS as bytes when they fit, else re-read from the ids
-    uint8_t* k8 = reinterpret_cast<uint8_t*>(lsm);
-    const bool staged = n <= kLdsSortMax * 8;
-    if (staged) stage_keys(R, n, k8);
-    __syncthreads();
-    for (int t0 = wbeg; t0 < wend; t0 += kWave) {  // counts: peers per tile, no LDS atomics
-      const int i = t0 + lane;
-      const bool act = i < wend;
-      const uint32_t d = act ? (staged ? k8[i] : region_key(R, i)) : 0u;
-      count_peers(hist, d, digit_peers(d, act, bits), w);
-    }
-    scan_digit_counts(hist, wsum);
-    for (int t0 = wbeg; t0 < wend; t0 += kWave) {
-      const int i = t0 + lane;
-      const bool act = i < wend;
-      const uint32_t d = act ? (staged ? k8[i] : region_key(R, i)) : 0u;
-      const uint64_t m = digit_peers(d, act, bits);
-      if (act) {
-        uint32_t* slot = &hist[d * kHistStride + w];
-        const uint32_t off = *slot;
-        region_store(R, static_cast<int>(off + __builtin_popcountll(m & lt)), static_cast<uint32_t>(i), d);
-        if (__builtin_ctzll(m) == lane) *slot = off + __builtin_popcountll(m);
-      }
-    }
-    return;
-  }
-  // n <= kLdsSortMax (host-checked): keys in LDS, LSD passes of <= 8 bits
-  stage_keys(R, n, lkey);
-  for (int i = tid; i < n; i += kLsThreads) pbuf0[i] = static_cast<uint16_t>(i);
-  const int passes = (bits + 7) / 8;
-  const int width = (bits + passes - 1) / passes;
-  const uint32_t dmask = (1u << width) - 1u;
-  int cur = 0;
-  for (int p = 0; p < passes; ++p) {
-    const int sh = p * width;
-    if (p > 0)
-      for (int e = tid; e < 256 * kHistStride; e += kLsThreads) hist[e] = 0u;
-    __syncthreads();
-    uint16_t pos[kLsTiles];
-    uint32_t dig[kLsTiles];
-    uint64_t peer[kLsTiles];  // lanes of the tile with the same digit, reused by the scatter
-    const uint16_t* src = cur ? pbuf1 : pbuf0;
-    uint16_t* dst = cur ? pbuf0 : pbuf1;
-#pragma unroll
-    for (int q = 0; q < kLsTiles; ++q) {
-      const int i = wbeg + q * kWave + lane;
-      pos[q] = 0;
-      dig[q] = 0;
-      if (i < wend) {
-        pos[q] = src[i];
-        dig[q] = (lkey[pos[q]] >> sh) & dmask;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kLsTiles; ++q) {
-      peer[q] = 0;
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        peer[q] = digit_peers(dig[q], wbeg + q * kWave + lane < wend, width);
-        count_peers(hist, dig[q], peer[q], w);
-      }
-    }
-    scan_digit_counts(hist, wsum);
-    const bool last = p == passes - 1;
-#pragma unroll
-    for (int q = 0; q < kLsTiles; ++q) {
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        const uint64_t m = peer[q];
-        if (m != 0) {
-          uint32_t* slot = &hist[dig[q] * kHistStride + w];
-          const uint32_t off = *slot;
-          const uint32_t o = off + __builtin_popcountll(m & lt);
-          if (last) region_store(R, static_cast<int>(o), pos[q], lkey[pos[q]]);
-          else dst[o] = pos[q];
-          if (__builtin_ctzll(m) == lane) *slot = off + __builtin_popcountll(m);
-        }
-      }
-    }
-    cur ^= 1;
-    __syncthreads();  // the scatter is complete before hist is cleared / the order read
+  StHist::scan(hist, wsum);
+  for (int t0 = s.beg; t0 < s.end; t0 += kWave) {
+    const int i = t0 + lane;
+    const bool act = i < s.end;
+    const uint32_t d = act ? (staged ? k8[i] : region_key(R, i)) : 0u;
+    const uint64_t m = digit_peers(d, act, bits);
+    if (act)
+      StHist::place(hist, d, m, w, [&](uint32_t o) { region_store(R, static_cast<int>(o), static_cast<uint32_t>(i), d); });
   }
 }
 
@@ -480,9 +359,9 @@ __global__ void __launch_bounds__(kLsThreads) region_sort_kernel(const Job j) {
 // (row key, position), spread over many small workgroups so that it finishes
 // in a few microseconds wherever the graph places it and sits beside other
 // kernels on a CU (~13 KB of LDS instead of 150 KB).
-//   chunk_sort_kernel: one 256-thread workgroup per kChunk consecutive
-//   positions of a region sorts them in LDS (the LSD passes above, 8 tiles per
-//   wave) into the key/value staging buffers: chunk-sorted row keys and
+//   chunk_sort_kernel: one 512-thread workgroup per kChunk consecutive
+//   positions of a region sorts them in LDS (LSD passes of tt_wg_sort.h, 4
+//   tiles per wave) into the key/value staging buffers: chunk-sorted row keys and
 //   region positions; small tables (<= 8 key bits) also write the chunk's
 //   digit counts.
 //   chunk_merge_kernel: the final slot of a chunk's i-th element with row key
@@ -495,7 +374,7 @@ constexpr int kChunk = 2048;
 constexpr int kCsThreads = 512;
 constexpr int kCsWaves = kCsThreads / kWave;
 constexpr int kCsTiles = kChunk / kCsThreads;
-constexpr int kCsHistStride = kCsWaves + 1;
+using CsHist = DigitHist<kCsWaves>;
 constexpr int kChunkMaxSmall = 64 * kChunk;  // small tables: the merge reads every chunk's counts
 
 __device__ __forceinline__ int table_of_chunk(const Job& j, int c) {
@@ -506,60 +385,12 @@ __device__ __forceinline__ int table_of_chunk(const Job& j, int c) {
   return __builtin_amdgcn_readfirstlane(t);
 }
 
-__device__ __forceinline__ Region region_of(const Job& j, int t) {
-  const TableDesc& T = j.t[t];
-  Region R;
-  R.ids0 = T.ids[0];
-  R.ids1 = T.ids[1];
-  R.ids2 = T.ids[2];
-  R.ids3 = T.ids[3];
-  R.batch = j.batch;
-  R.keys = const_cast<uint32_t*>(j.keys) + T.base;
-  R.vals = const_cast<uint32_t*>(j.vals) + T.base;
-  R.n = T.n;
-  R.nr = static_cast<uint32_t>(T.num_rows);
-  R.khi = static_cast<uint32_t>(t) << j.id_bits;
-  R.invalid = (1u << j.id_bits) - 1u;
-  return R;
-}
-
-// hist[digit][wave] (row stride kCsHistStride) -> exclusive offsets in
-// (digit, wave) order; 4 entries per thread
-__device__ __forceinline__ void cs_scan_counts(uint32_t* hist, uint32_t* wsum) {
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
-  __syncthreads();
-  uint32_t h[4], run = 0;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int L = 4 * tid + u;
-    h[u] = hist[(L / kCsWaves) * kCsHistStride + L % kCsWaves];
-    run += h[u];
-  }
-  uint32_t inc = run;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o, kWave);
-    if (lane >= o) inc += y;
-  }
-  if (lane == kWave - 1) wsum[w] = inc;
-  __syncthreads();
-  uint32_t ex = inc - run;
-  for (int v = 0; v < w; ++v) ex += wsum[v];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int L = 4 * tid + u;
-    hist[(L / kCsWaves) * kCsHistStride + L % kCsWaves] = ex;
-    ex += h[u];
-  }
-  __syncthreads();
-}
-
 __global__ void __launch_bounds__(kCsThreads) chunk_sort_kernel(const Job j) {
   __shared__ uint32_t lkey[kChunk];
   __shared__ uint16_t pbuf[2][kChunk];
-  __shared__ uint32_t hist[256 * kCsHistStride];
+  __shared__ uint32_t hist[CsHist::kWords];
   __shared__ uint32_t wsum[kCsWaves];
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
+  const int tid = threadIdx.x;
   const int t = table_of_chunk(j, blockIdx.x);
   const Region R = region_of(j, t);
   const int c0 = (static_cast<int>(blockIdx.x) - j.t[t].chunk_begin) * kChunk;
@@ -567,14 +398,7 @@ __global__ void __launch_bounds__(kCsThreads) chunk_sort_kernel(const Job j) {
   uint32_t* ck = j.keys_in + j.t[t].base + c0;  // chunk-sorted row keys
   uint32_t* cp = j.vals_in + j.t[t].base + c0;  // their region positions
   if (tid < n / kBlock) j.arrived[(j.t[t].base + c0) / kBlock + tid] = 0u;  // this call's join counters
-  if (blockIdx.x == 0 && tid == 0) {  // stamp the workspace with this call's fingerprint
-    if (j.hdr->magic != kHdrMagic) {
-      j.hdr->error = 0u;
-      j.hdr->magic = kHdrMagic;
-    }
-    j.hdr->fp0 = j.fp0;
-    j.hdr->fp1 = j.fp1;
-  }
+  if (blockIdx.x == 0 && tid == 0) stamp_header(j);
   {  // row keys of the chunk: kCsTiles independent id loads in flight per thread
     uint32_t k[kCsTiles];
 #pragma unroll
@@ -588,70 +412,38 @@ __global__ void __launch_bounds__(kCsThreads) chunk_sort_kernel(const Job j) {
       }
     }
   }
-  for (int e = tid; e < 256 * kCsHistStride; e += kCsThreads) hist[e] = 0u;
+  CsHist::clear(hist);
   const int bits = 32 - __builtin_clz(R.nr);  // row keys lie in [0, nr]
-  const int per = ((n + kCsWaves - 1) / kCsWaves + kWave - 1) / kWave * kWave;
-  const int wbeg = w * per, wend = min(n, wbeg + per);
-  const uint64_t lt = (uint64_t(1) << lane) - 1u;
+  const WaveSlice<kCsWaves> s(n);
   const int passes = (bits + 7) / 8;
   const int width = (bits + passes - 1) / passes;
   const uint32_t dmask = (1u << width) - 1u;
   int cur = 0;
   for (int p = 0; p < passes; ++p) {
-    const int sh = p * width;
-    if (p > 0)
-      for (int e = tid; e < 256 * kCsHistStride; e += kCsThreads) hist[e] = 0u;
+    if (p > 0) CsHist::clear(hist);
     __syncthreads();
-    uint16_t pos[kCsTiles];
-    uint32_t dig[kCsTiles];
-    uint64_t peer[kCsTiles];
-#pragma unroll
-    for (int q = 0; q < kCsTiles; ++q) {
-      const int i = wbeg + q * kWave + lane;
-      pos[q] = 0;
-      dig[q] = 0;
-      if (i < wend) {
-        pos[q] = pbuf[cur][i];
-        dig[q] = (lkey[pos[q]] >> sh) & dmask;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kCsTiles; ++q) {
-      peer[q] = 0;
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        peer[q] = digit_peers(dig[q], wbeg + q * kWave + lane < wend, width);
-        if (peer[q] != 0 && __builtin_ctzll(peer[q]) == lane) hist[dig[q] * kCsHistStride + w] += __builtin_popcountll(peer[q]);
-      }
-    }
-    const bool last = p == passes - 1;
+    LsdPass<kCsWaves, kCsTiles> pass;
+    pass.load(s, pbuf[cur], lkey, p * width, dmask);
+    pass.count(s, hist, width);
     if (passes == 1) {  // small table: the chunk's digit counts (block-uniform)
       __syncthreads();
       if (tid < 256) {
-        uint32_t s = 0;
+        uint32_t c = 0;
 #pragma unroll
-        for (int v = 0; v < kCsWaves; ++v) s += hist[tid * kCsHistStride + v];
-        j.chunk_hist[static_cast<int64_t>(blockIdx.x) * 256 + tid] = s;
+        for (int v = 0; v < kCsWaves; ++v) c += hist[tid * CsHist::kStride + v];
+        j.chunk_hist[static_cast<int64_t>(blockIdx.x) * 256 + tid] = c;
       }
     }
-    cs_scan_counts(hist, wsum);
-#pragma unroll
-    for (int q = 0; q < kCsTiles; ++q) {
-      if (wbeg + q * kWave < wend) {  // wave-uniform
-        const uint64_t m = peer[q];
-        if (m != 0) {
-          uint32_t* slot = &hist[dig[q] * kCsHistStride + w];
-          const uint32_t off = *slot;
-          const uint32_t o = off + __builtin_popcountll(m & lt);
-          if (last) {
-            ck[o] = lkey[pos[q]];
-            cp[o] = static_cast<uint32_t>(c0) + pos[q];
-          } else {
-            pbuf[cur ^ 1][o] = pos[q];
-          }
-          if (__builtin_ctzll(m) == lane) *slot = off + __builtin_popcountll(m);
-        }
+    CsHist::scan(hist, wsum);
+    const bool last = p == passes - 1;
+    pass.scatter(s, hist, [&](uint32_t o, uint16_t ps) {
+      if (last) {
+        ck[o] = lkey[ps];
+        cp[o] = static_cast<uint32_t>(c0) + ps;
+      } else {
+        pbuf[cur ^ 1][o] = ps;
       }
-    }
+    });
     cur ^= 1;
     __syncthreads();  // the scatter is complete before hist is cleared / the order read
   }
@@ -1254,20 +1046,6 @@ size_t tables_ws_bytes(const tt_sparse_table* tables, int32_t num_tables, int64_
   return total;
 }
 
-// TT_SPARSE_SORT: "chunk" (default: chunked LDS sort when every region fits),
-// "region" (one workgroup per region) or "device" (key build + rocPRIM sort
-// for every call).
-enum SortMode { kSortChunk = 0, kSortRegion = 1, kSortDevice = 2 };
-int sort_mode() {
-  static const int v = [] {
-    const char* e = std::getenv("TT_SPARSE_SORT");
-    if (e && std::strcmp(e, "device") == 0) return int(kSortDevice);
-    if (e && std::strcmp(e, "region") == 0) return int(kSortRegion);
-    return int(kSortChunk);
-  }();
-  return v;
-}
-
 // Stages: the key build + sort depends only on the ids, so a caller may run
 // it early on a side stream (kStageSort) and the gradient-dependent block
 // launch (sums, joins, applies) later (kStageApply) with the same tables, batch
@@ -1303,14 +1081,18 @@ int run_sparse(const tt_sparse_table* tables, int32_t num_tables, int64_t batch,
     j.dense_dim = dense_dim;
     j.hdr = w.hdr;
     if (stage != kStageApply) {
-      const int mode = sort_mode();
-      bool lds = mode != kSortDevice, chunked = mode == kSortChunk;
+      // by size alone: the chunked sort when every region fits its merge, else
+      // the small-table sort when every table is small (row keys of <= 8
+      // bits), else key build + rocPRIM
+      bool chunked = true, all_small = true;
       int merge_chunks = 0;  // most chunks of a large-key region: the merge's LDS
+      int staged = 0;        // longest region the small-table sort stages in LDS
       for (int i = 0; i < cnt; ++i) {
         const bool small = bits_for(j.t[i].num_rows) <= 8;
-        lds = lds && (j.t[i].n_pad <= kLdsSortMax || small);
-        chunked = chunked && (small ? j.t[i].n_pad <= kChunkMaxSmall : j.t[i].n_pad <= kChunkMaxLarge);
+        all_small = all_small && small;
+        chunked = chunked && j.t[i].n_pad <= (small ? kChunkMaxSmall : kChunkMaxLarge);
         if (!small) merge_chunks = std::max(merge_chunks, static_cast<int>(ceil_div(j.t[i].n_pad, kChunk)));
+        if (j.t[i].n_pad <= kStStageMax) staged = std::max(staged, j.t[i].n_pad);
       }
       if (chunked) {
         hipLaunchKernelGGL(chunk_sort_kernel, dim3(j.num_chunks), dim3(kCsThreads), 0, st, j);
@@ -1321,11 +1103,12 @@ int run_sparse(const tt_sparse_table* tables, int32_t num_tables, int64_t batch,
         hipLaunchKernelGGL(chunk_merge_kernel, dim3(j.num_chunks), dim3(kCsThreads), merge_chunks * kChunk * 4, st,
                            j);
         TT_CHECK_LAUNCH();
-      } else if (lds) {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(region_sort_kernel),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLsLdsBytes);
+      } else if (all_small) {
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void*>(small_table_sort_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, StHist::kWords * 4 + kStStageMax);
         TT_CHECK_HIP(attr);
-        hipLaunchKernelGGL(region_sort_kernel, dim3(cnt), dim3(kLsThreads), kLsLdsBytes, st, j);
+        hipLaunchKernelGGL(small_table_sort_kernel, dim3(cnt), dim3(kStThreads), StHist::kWords * 4 + staged, st, j);
         TT_CHECK_LAUNCH();
       } else {
         hipLaunchKernelGGL(build_keys_kernel, dim3(ceil_div(p.total, kThreads)), dim3(kThreads), 0, st, j, p.total);
@@ -1556,14 +1339,7 @@ __global__ void __launch_bounds__(kRoutedThreads) routed_keys_kernel(const Job j
     }
   }
   if (i < r.total + r.pad_begin[r.num_tables] && i % kBlock == 0) j.arrived[i / kBlock] = 0u;  // join counters
-  if (i == 0) {  // stamp the workspace with this call's fingerprint
-    if (j.hdr->magic != kHdrMagic) {
-      j.hdr->error = 0u;
-      j.hdr->magic = kHdrMagic;
-    }
-    j.hdr->fp0 = j.fp0;
-    j.hdr->fp1 = j.fp1;
-  }
+  if (i == 0) stamp_header(j);
 }
 
 dim3 stride_grid(int64_t n) {

@@ -587,6 +587,37 @@ def test_sparse_adagrad_sort_paths_bitexact(cuda, rows, sources, B):
     assert np.array_equal(ta.cpu().numpy(), ref_acc)
 
 
+def test_sparse_adagrad_small_tables_staged_and_unstaged_bitexact(cuda):
+    """Two tables of <= 255 rows in one call: 200 rows x 4 sources x 33000 =
+    132000 lookups (> 131072) pushes the call off the chunked sort onto the
+    one-workgroup counting sort and is itself too long for that kernel's byte
+    staging (it re-reads its ids); 255 rows x 1 source x 33000 lookups is
+    staged in LDS as bytes.  Both bit-exact vs the restatement per table."""
+    rng = np.random.default_rng(33000)
+    D, B = 8, 33000
+    shapes = [(200, 4), (255, 1)]
+    grad = rng.standard_normal((B, D * sum(s for _, s in shapes))).astype(np.float32)
+    tables, refs, col = [], [], 0
+    for rows, sources in shapes:
+        w = rng.uniform(-0.05, 0.05, (rows, D)).astype(np.float32)
+        acc = np.full((rows, D), 0.1, np.float32)
+        ids = [zipf_ids(rng, B, rows) for _ in range(sources)]
+        ids[0][::97] = -3
+        ids[-1][5::101] = rows
+        offs = [col + D * s for s in range(sources)]
+        ref_w, ref_acc = w.copy(), acc.copy()
+        oracle.sparse_adagrad(ref_w, ref_acc, np.concatenate(ids),
+                              np.concatenate([grad[:, o:o + D] for o in offs]), 0.05, 1e-7)
+        tw, ta = _t(w, cuda), _t(acc, cuda)
+        tables.append(dict(table=tw, slot0=ta, ids=[_t(i, cuda) for i in ids], grad_col_offset=offs))
+        refs.append((tw, ta, ref_w, ref_acc))
+        col += D * sources
+    hip_ops.sparse_adagrad(tables, B, _t(grad, cuda), 0.05, 1e-7)
+    for tw, ta, ref_w, ref_acc in refs:
+        assert np.array_equal(tw.cpu().numpy(), ref_w)
+        assert np.array_equal(ta.cpu().numpy(), ref_acc)
+
+
 @pytest.mark.parametrize("n", [16384, 16385, 20000, 40000])
 def test_sparse_adagrad_mostly_invalid_ids_bitexact(cuda, n):
     """Lookups whose ids are mostly outside the table (the owner-side update
