@@ -441,6 +441,8 @@ _PROTOS = {
     "tt_l2norm_rows_grad": (c_int32, [c_void_p, c_int32, c_void_p]),
     "tt_gather_bag": (c_int32, [POINTER(BagJob), c_int32, c_int64, c_void_p]),
     "tt_bag_grad_expand": (c_int32, [POINTER(BagGradJob), c_int32, c_int64, c_void_p]),
+    "tt_inbatch_weight_rows": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_int32, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

@@ -24,7 +24,35 @@ from pkg.schema.features import Feature
 from pkg.modelling.device import default_device
 from pkg.modelling import hip_ops
 
-__all__ = ["EncodedDataset", "DeviceDataset", "encode_dataframe", "epoch_order"]
+__all__ = ["EncodedDataset", "DeviceDataset", "EncodedColumns", "encode_dataframe", "epoch_order", "WEIGHT_KEY"]
+
+# per-example sample weights, normalised to [0, 1] (two_tower_model.WEIGHT_KEY)
+WEIGHT_KEY = "__weight__"
+# the shard entry that keeps a weighted dataset's w_max
+_WEIGHT_SCALE_ENTRY = "__weight_scale__"
+
+
+class EncodedColumns(dict):
+    """encode_dataframe's columns; weight_scale is the w_max its "__weight__"
+    column was divided by (None without sample weights)."""
+
+    weight_scale: Optional[float] = None
+
+
+def _normalised_weights(w) -> tuple:
+    """(float32 w / float32 w_max, w_max) of the sample weights w, checked on
+    the host: finite, >= 0 and not all zero."""
+    w = np.asarray(w)
+    if w.ndim != 1 or w.dtype.kind not in "fiub":
+        raise ValueError(f"sample_weight must be a 1-D numeric column, got dtype {w.dtype} shape {w.shape}")
+    w = w.astype(np.float32)
+    bad = np.flatnonzero(~np.isfinite(w) | (w < 0))
+    if bad.size:
+        raise ValueError(f"sample_weight: row {int(bad[0])} holds {w[bad[0]]!r}; weights must be finite and >= 0")
+    w_max = np.float32(w.max()) if w.size else np.float32(0)
+    if not w_max > 0:
+        raise ValueError("sample_weight: every weight is zero (row 0 holds 0.0); at least one must be positive")
+    return w / w_max, float(w_max)
 
 
 def epoch_order(num_rows: int, shuffle_size: Optional[int], seed: int, epoch: int) -> np.ndarray:
@@ -43,13 +71,18 @@ def epoch_order(num_rows: int, shuffle_size: Optional[int], seed: int, epoch: in
 
 def encode_dataframe(df: pd.DataFrame, features: Sequence[Feature],
                      extra: Optional[Dict[str, np.ndarray]] = None, logq=None,
-                     candidate_col: Optional[str] = None) -> Dict[str, np.ndarray]:
+                     candidate_col: Optional[str] = None, sample_weight=None) -> Dict[str, np.ndarray]:
     """Encode a DataFrame with the schema's features (StringLookup on the host,
     libtt's multi-threaded hash table).  logq: a LogQCorrection (or its
     {id: p} dict) — adds the exact per-example "__logq__" column from the raw
     candidate ids (logq_correction.py:66-71), needed when the probability
-    lookup covers ids outside the candidate vocab."""
-    cols: Dict[str, np.ndarray] = {}
+    lookup covers ids outside the candidate vocab.  sample_weight: a column
+    name of df or an array of per-example weights (Keras
+    fit(sample_weight=...)) — finite, >= 0 and not all zero, else ValueError
+    naming the first offending row; stored as "__weight__" = float32(w) /
+    float32(w_max) in [0, 1], with w_max in the returned columns'
+    weight_scale, which EncodedDataset keeps and TwoTowerModel.fit reads."""
+    cols: Dict[str, np.ndarray] = EncodedColumns()
     if logq is not None:
         from pkg.modelling.layers.logq_correction import LogQCorrection
 
@@ -66,6 +99,11 @@ def encode_dataframe(df: pd.DataFrame, features: Sequence[Feature],
             cols[f.name] = df[f.name].values.astype(np.float32)
     for k, v in (extra or {}).items():
         cols[k] = np.asarray(v)
+    if sample_weight is not None:
+        w = df[sample_weight].values if isinstance(sample_weight, str) else sample_weight
+        if len(w) != len(df):
+            raise ValueError(f"sample_weight has {len(w)} rows, the frame {len(df)}")
+        cols[WEIGHT_KEY], cols.weight_scale = _normalised_weights(w)
     return cols
 
 
@@ -74,10 +112,12 @@ class EncodedDataset:
 
     def __init__(self, columns: Dict[str, np.ndarray], batch_size: Optional[int] = None,
                  shuffle_size: Optional[int] = None, seed: int = 0, device: Optional[torch.device] = None,
-                 fn: Optional[Callable] = None):
+                 fn: Optional[Callable] = None, weight_scale: Optional[float] = None):
         lens = {len(v) for v in columns.values()}
         if len(lens) > 1:
             raise ValueError(f"columns have different lengths: {lens}")
+        # w_max of the "__weight__" column (encode_dataframe's; None: no recorded scale)
+        self.weight_scale = weight_scale if weight_scale is not None else getattr(columns, "weight_scale", None)
         self.columns = {k: np.ascontiguousarray(v) for k, v in columns.items()}
         self.num_rows = lens.pop() if lens else 0
         self.batch_size = batch_size
@@ -94,7 +134,7 @@ class EncodedDataset:
     def map(self, fn: Callable) -> "EncodedDataset":
         prev = self.fn
         new = EncodedDataset(self.columns, self.batch_size, self.shuffle_size, self.seed, self.device,
-                             (lambda b: fn(prev(b))) if prev else fn)
+                             (lambda b: fn(prev(b))) if prev else fn, self.weight_scale)
         return new
 
     def _order(self) -> np.ndarray:
@@ -120,7 +160,10 @@ class EncodedDataset:
         paths = []
         for i, s in enumerate(range(0, max(self.num_rows, 1), step)):
             p = os.path.join(dirpath, f"part-{i:05d}.npz")
-            np.savez(p, **{k: v[s:s + step] for k, v in self.columns.items()})
+            part = {k: v[s:s + step] for k, v in self.columns.items()}
+            if self.weight_scale is not None:  # every shard carries the dataset's w_max
+                part[_WEIGHT_SCALE_ENTRY] = np.asarray([self.weight_scale], np.float64)
+            np.savez(p, **part)
             paths.append(p)
         return paths
 
@@ -131,12 +174,18 @@ class EncodedDataset:
         if not files:
             raise FileNotFoundError(f"no .npz shards in {dirpath}")
         parts: Dict[str, List[np.ndarray]] = {}
+        scales = set()
         for p in files:
             with np.load(p, allow_pickle=False) as z:
                 for k in z.files:
+                    if k == _WEIGHT_SCALE_ENTRY:
+                        scales.add(float(z[k][0]))
+                        continue
                     parts.setdefault(k, []).append(z[k])
+        if len(scales) > 1:
+            raise ValueError(f"shards in {dirpath} were saved with different sample-weight scales: {sorted(scales)}")
         cols = {k: np.concatenate(v) for k, v in parts.items()}
-        return cls(cols, batch_size, shuffle_size, seed, device)
+        return cls(cols, batch_size, shuffle_size, seed, device, weight_scale=scales.pop() if scales else None)
 
 
 class DeviceDataset:
@@ -155,7 +204,8 @@ class DeviceDataset:
 
     def __init__(self, columns: Dict[str, np.ndarray], batch_size: Optional[int] = None,
                  shuffle_size: Optional[int] = None, seed: int = 0, device: Optional[torch.device] = None,
-                 fn: Optional[Callable] = None, _shared=None):
+                 fn: Optional[Callable] = None, _shared=None, weight_scale: Optional[float] = None):
+        self.weight_scale = weight_scale if weight_scale is not None else getattr(columns, "weight_scale", None)
         self.batch_size = batch_size
         self.shuffle_size = shuffle_size
         self.seed = seed
@@ -206,7 +256,8 @@ class DeviceDataset:
 
     @classmethod
     def from_encoded(cls, ds: EncodedDataset, device: Optional[torch.device] = None) -> "DeviceDataset":
-        return cls(ds.columns, ds.batch_size, ds.shuffle_size, ds.seed, device or ds.device, ds.fn)
+        return cls(ds.columns, ds.batch_size, ds.shuffle_size, ds.seed, device or ds.device, ds.fn,
+                   weight_scale=ds.weight_scale)
 
     @classmethod
     def load(cls, dirpath: str, batch_size: Optional[int] = None, shuffle_size: Optional[int] = None,
@@ -225,7 +276,8 @@ class DeviceDataset:
     def map(self, fn: Callable) -> "DeviceDataset":
         prev = self.fn
         return DeviceDataset({}, self.batch_size, self.shuffle_size, self.seed,
-                             fn=(lambda b: fn(prev(b))) if prev else fn, _shared=self._shared())
+                             fn=(lambda b: fn(prev(b))) if prev else fn, _shared=self._shared(),
+                             weight_scale=self.weight_scale)
 
     def __len__(self) -> int:
         bs = self.batch_size or 1

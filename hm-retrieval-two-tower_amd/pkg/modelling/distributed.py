@@ -1256,6 +1256,10 @@ class ShardedTrainStep:
         """One step on `batch` (next_batch / ahead: accepted for API
         compatibility and ignored — routing is part of the step's graph)."""
         tm = time.perf_counter()
+        if "__weight__" in batch:  # two_tower_model.WEIGHT_KEY
+            raise NotImplementedError("ShardedTrainStep does not support sample weights (batch key '__weight__'); "
+                                      "the loss-level sharded form is losses.global_inbatch_grads(weights=...), and "
+                                      "the single-device steps take weighted batches")
         if self._static is None:
             self._setup(batch)
         self._load(batch)

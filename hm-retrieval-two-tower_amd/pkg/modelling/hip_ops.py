@@ -31,6 +31,7 @@ __all__ = [
     "dense_adam",
     "inbatch_rows",
     "inbatch_cols",
+    "inbatch_weight_rows",
     "inbatch_fused",
     "inbatch_fused_workspace",
     "inbatch_prep",
@@ -901,6 +902,35 @@ def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Opti
     check(fn(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
              _opt_ptr(logq, "logq", C), pos_offset, dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return dc
+
+
+def inbatch_weight_rows(w: torch.Tensor, lse: torch.Tensor, row_loss: torch.Tensor,
+                        dq: Optional[torch.Tensor] = None):
+    """Per-example sample weights folded in between inbatch_rows and
+    inbatch_cols (tt_inbatch_weight_rows, one launch): (lse_w [R],
+    row_loss_w [R], wloss [R]).  w [R]: the normalised weights in [0, 1];
+    lse, row_loss: inbatch_rows' outputs.  inbatch_cols(q, lse_w, ...,
+    row_loss=row_loss_w) then returns the weighted loss's dc, and wloss holds
+    the weighted loss terms w_i * row_loss_i.  dq [R, E] (inbatch_rows'), if
+    given, is scaled by w IN PLACE (a weight-0 row stored as zeros, a
+    weight-1 row not touched).  A weight outside [0, 1] gives NaN in its row.
+    The three outputs are views of a Workspace buffer (a captured step keeps
+    their addresses): the next call in the same scope overwrites them."""
+    _req(w, "w", torch.float32, 1)
+    n = w.numel()
+    pw, pl, pr = _opt_ptr(w, "w", n), _opt_ptr(lse, "lse", n), _opt_ptr(row_loss, "row_loss", n)
+    lddq, dim = 0, 0
+    if dq is not None:
+        _req(dq, "dq", torch.float32, 2)
+        if dq.shape[0] != n:
+            raise ValueError(f"dq must have one row per weight ({n}), got shape {tuple(dq.shape)}")
+        lddq, dim = _row_major(dq, "dq"), dq.shape[1]
+    seg = (n + 63) // 64 * 64  # each output 256-B aligned
+    out = Workspace.get(3 * seg * 4, w.device, "inbatch_weight")[:3 * seg * 4].view(torch.float32)
+    lse_w, row_loss_w, wloss = (out[i * seg:i * seg + n] for i in range(3))
+    check(lib().tt_inbatch_weight_rows(pw, pl, pr, n, lse_w.data_ptr(), row_loss_w.data_ptr(), wloss.data_ptr(),
+                                       dq.data_ptr() if dq is not None else None, lddq, dim, _stream()))
+    return lse_w, row_loss_w, wloss
 
 
 def inbatch_fused_workspace(B: int, E: int, device: torch.device) -> torch.Tensor:

@@ -21,7 +21,7 @@ import torch
 from pkg.modelling import hip_ops
 
 __all__ = ["InBatchSoftmaxCrossEntropy", "inbatch_softmax_xent", "towers_inbatch_softmax_xent",
-           "global_inbatch_grads", "global_towers_inbatch_softmax_xent", "TOWER_C_SCOPE"]
+           "global_inbatch_grads", "global_towers_inbatch_softmax_xent", "weighted_inbatch_grads", "TOWER_C_SCOPE"]
 
 
 def x3_scores() -> bool:
@@ -49,10 +49,36 @@ def x3_scores() -> bool:
 # as one candidate.  The reference has no such option: ids=None is its loss.
 
 
+# weights (every loss below, optional): per-example sample weights, an fp32
+# [B] device tensor of NORMALISED weights w_i / w_max in [0, 1], with
+# weight_scale = w_max (TensorFlow Recommenders' Retrieval task sample_weight,
+# Keras fit(sample_weight=...)): the loss is sum_i w_max w_i l_i, "mean"
+# divides by B (Keras' rule).  The pass kernels do not change: the rows pass
+# runs as it is, hip_ops.inbatch_weight_rows folds w into the lse and row_loss
+# the cols pass reads and scales dq in place (one launch), the cols pass
+# returns the weighted dc, and w_max goes into the loss scale and the
+# backward's scalar (include/tt.h, tt_inbatch_weight_rows).  A weight outside
+# [0, 1] turns the loss NaN.  weights=None issues the calls it always issued.
+
+
+def weighted_inbatch_grads(q, c, logq, weights, ids=None, x3: Optional[bool] = None):
+    """(wloss [B], dq, dc) of the weighted single-device loss: rows, fold,
+    cols, with the operands and ids the unweighted entries take."""
+    x3 = x3_scores() if x3 is None else x3
+    lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids)
+    lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
+    dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids)
+    return wloss, dq, dc
+
+
 class _InBatchXent(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, c, logq, scale, ids=None):
-        lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids)
+    def forward(ctx, q, c, logq, scale, ids=None, weights=None, weight_scale=1.0):
+        if weights is not None:
+            scale = scale * weight_scale
+            row_loss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids)
+        else:
+            lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids)
         ctx.scale = scale
         ctx.save_for_backward(dq, dc)
         return hip_ops.loss_sum(row_loss, scale)
@@ -61,7 +87,7 @@ class _InBatchXent(torch.autograd.Function):
     def backward(ctx, g):
         dq, dc = ctx.saved_tensors
         s = g * ctx.scale
-        return dq * s, dc * s, None, None, None
+        return dq * s, dc * s, None, None, None, None, None
 
 
 _SIDE: dict = {}
@@ -192,20 +218,21 @@ class _TowersInBatchXent(torch.autograd.Function):
     a device scalar (no separate scaling pass over dQ, dC)."""
 
     @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None):
+    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None,
+                weights=None, weight_scale=1.0):
         ctx.pair = _paired(qi, stack_q, stack_c)
         ctx.on_dx = on_dx
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
             return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower,
-                                              ids=ids)
+                                              ids=ids, weights=weights, weight_scale=weight_scale)
         main = torch.cuda.current_stream()
         side = _tower_stream(qi.device)
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
         # (not under x3_scores() or with ids: those entries prepare their operands themselves;
         # not with normalised outputs: it would prepare the un-normalised ones)
-        split_prep = (SPLIT_PREP and not x3_scores() and ids is None
+        split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None
                       and not (stack_q.normalize or stack_c.normalize))
         ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
@@ -218,10 +245,13 @@ class _TowersInBatchXent(torch.autograd.Function):
             hip_ops.inbatch_prep(qa[-1], 0, None, ws)
         main.wait_stream(side)
         return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws,
-                                          ids)
+                                          ids, weights, weight_scale)
 
     @staticmethod
-    def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None, ids=None):
+    def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None, ids=None,
+                weights=None, weight_scale=1.0):
+        if weights is not None:
+            scale = scale * weight_scale  # w_max: the loss is linear in w
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
         ctx.scale = scale
@@ -230,7 +260,10 @@ class _TowersInBatchXent(torch.autograd.Function):
         # outputs (one launch for both), and its gradients are taken back to
         # the un-normalised ones right after it (one launch, in place)
         q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])
-        if ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
+        if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
+            wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids)
+            loss = hip_ops.loss_sum(wloss, scale)
+        elif ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
             _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids)
         elif x3_scores():  # fp32-faithful scores (its own preparation and workspace)
             _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=True)
@@ -250,7 +283,7 @@ class _TowersInBatchXent(torch.autograd.Function):
         stack_q, stack_c = ctx.stacks
         if ctx.pair:  # (on_dx unused: on_tower then applies each tower's whole update)
             return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, ctx.on_tower),
-                    None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None, None)
         on_dx = ctx.on_dx
         main = torch.cuda.current_stream()
         side = _tower_stream(dq.device)
@@ -267,11 +300,12 @@ class _TowersInBatchXent(torch.autograd.Function):
         if ctx.on_tower is not None:
             ctx.on_tower(0, gqi, gflat_q)
         main.wait_stream(side)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None
 
 
 def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], comm,
-                         rows=None, cols=None, x3: Optional[bool] = None, ids: Optional[torch.Tensor] = None):
+                         rows=None, cols=None, x3: Optional[bool] = None, ids: Optional[torch.Tensor] = None,
+                         weights: Optional[torch.Tensor] = None, fold=None):
     """This rank's share of the in-batch loss over the GLOBAL batch
     (two_tower_model.py:113-122 with the batch split over the ranks: row i's
     negatives are every candidate of every rank).  q, c: this rank's [b, E]
@@ -287,10 +321,18 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     rank's [b] int32 candidate ids — accidental hits removed over the global
     batch: the ids are all-gathered once, and the gathered vector is the rows
     pass's col_ids and the cols pass's row_ids (injected rows / cols receive
-    row_ids / col_ids as keywords)."""
+    row_ids / col_ids as keywords).  weights: this rank's [b] normalised
+    sample weights (normalised by the GLOBAL w_max, which the caller puts
+    into its loss scale) — the fold runs on the rank's own rows right after
+    the rows pass (fold(w, lse, row_loss, dq) -> (lse_w, row_loss_w, wloss),
+    dq scaled in place; hip_ops.inbatch_weight_rows unless injected), the
+    all-gather of [lse, row_loss] then carries the folded values and nothing
+    else moves; the first value returned is then wloss, the weighted terms.
+    The one-rank shortcut through the single-device entry is not taken."""
     if x3 is None:
         x3 = x3_scores()
-    if WORLD1_FUSED and comm.world == 1 and rows is None and cols is None and not getattr(comm, "always", False):
+    if (WORLD1_FUSED and weights is None and comm.world == 1 and rows is None and cols is None
+            and not getattr(comm, "always", False)):
         # one rank: its rows are every row and its columns every column — the
         # single-device entry (one shared preparation of q and c for both passes)
         _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids)
@@ -306,14 +348,16 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
         rows = functools.partial(rows, row_ids=ids, col_ids=I)
         cols = functools.partial(cols, row_ids=I, col_ids=ids)
     lse, row_loss, dq = rows(q, C, L, pos_offset=off)
+    if weights is not None:
+        lse, row_loss_w, wloss = (fold or hip_ops.inbatch_weight_rows)(weights, lse, row_loss, dq)
     Qa = comm.all_gather(q)                                    # [G b, E]
     if comm.world == 1 and not getattr(comm, "always", False):
-        lse_a, loss_a = lse, row_loss  # one rank: its rows are every row (no stack / split copies)
+        lse_a, loss_a = lse, (row_loss if weights is None else row_loss_w)  # one rank: its rows are every row (no stack / split copies)
     else:
-        st = comm.all_gather(torch.stack([lse, row_loss], 1))  # [G b, 2]: every row's lse and loss
+        st = comm.all_gather(torch.stack([lse, row_loss if weights is None else row_loss_w], 1))  # [G b, 2]: every row's lse and loss
         lse_a, loss_a = st[:, 0].contiguous(), st[:, 1].contiguous()
     dc = cols(Qa, lse_a, c, logq, pos_offset=off, row_loss=loss_a)  # local columns, every row
-    return row_loss, dq, dc
+    return (row_loss if weights is None else wloss), dq, dc
 
 
 class _GlobalTowersInBatchXent(torch.autograd.Function):
@@ -322,7 +366,10 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
     gradients) over the ranks."""
 
     @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm, ids=None):
+    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm, ids=None, weights=None,
+                weight_scale=1.0):
+        if weights is not None:
+            scale = scale * weight_scale
         ctx.pair = _paired(qi, stack_q, stack_c)
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
@@ -333,7 +380,7 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
             qa = stack_q.forward_acts(qi, flat_q)
             _tower_join(qi)
         q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])  # cosine scoring (as _TowersInBatchXent)
-        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids)
+        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids, weights=weights)
         unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
@@ -348,52 +395,64 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
         s = (g * ctx.scale if ctx.scale != 1.0 else g).reshape(1).float().contiguous()
         stack_q, stack_c = ctx.stacks
         if ctx.pair:
-            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None, None)
+            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None, None,
+                    None, None)
         with _TowerFork(dq):
             gci, gflat_c = stack_c.backward_acts(ca, flat_c, dc, s, ctx.needs_input_grad[1])
         gqi, gflat_q = stack_q.backward_acts(qa, flat_q, dq, s, ctx.needs_input_grad[0])
         _tower_join(dq)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None
 
 
 def global_towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c, comm,
                                        logq: Optional[torch.Tensor] = None,
-                                       ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                       ids: Optional[torch.Tensor] = None,
+                                       weights: Optional[torch.Tensor] = None,
+                                       weight_scale: float = 1.0) -> torch.Tensor:
     """towers_inbatch_softmax_xent with the negatives of every rank (SUM
     reduction, the reference's runner.py:78-83).  ids: this rank's candidate
-    ids (accidental hits removed over the global batch)."""
-    return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm, ids)
+    ids (accidental hits removed over the global batch).  weights: this
+    rank's normalised sample weights, weight_scale the global w_max."""
+    return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm, ids,
+                                          weights, float(weight_scale))
 
 
 def towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c,
                                 logq: Optional[torch.Tensor] = None, reduction: str = "sum",
-                                on_tower=None, on_dx=None, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                on_tower=None, on_dx=None, ids: Optional[torch.Tensor] = None,
+                                weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0) -> torch.Tensor:
     """Loss of the query tower on qi against the candidate tower on ci (tower
     inputs [B, *]), fused into one autograd node; stack_* are DenseStacks.
     on_tower(i, input_grad, flat_grad), if given, is called in the backward as
     soon as tower i's (0 query, 1 candidate) gradients exist, on the stream and
     workspace scope they were produced in (the fused train step applies the
-    optimizer there).  ids [B] (int32): accidental hits removed."""
+    optimizer there).  ids [B] (int32): accidental hits removed.  weights [B]
+    (fp32, in [0, 1]) and weight_scale: sample weights (see above)."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / qi.shape[0]
     return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, on_tower,
-                                    on_dx, ids)
+                                    on_dx, ids, weights, float(weight_scale))
 
 
 def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor] = None,
-                         reduction: str = "sum", ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         reduction: str = "sum", ids: Optional[torch.Tensor] = None,
+                         weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0) -> torch.Tensor:
     """Loss of query rows q [B,E] against candidates c [B,E] (positive of row
     i is column i), logq [B] the per-candidate log sampling probability.
-    ids [B] (int32): accidental hits removed (see above)."""
+    ids [B] (int32): accidental hits removed (see above).  weights [B] (fp32,
+    in [0, 1]) and weight_scale: sample weights (see above)."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / q.shape[0]
     if not q.requires_grad and not c.requires_grad:
         # the scores the training loss is computed from, in either mode
         lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids, col_ids=ids)
+        if weights is not None:
+            _, _, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss)
+            return hip_ops.loss_sum(wloss, scale * weight_scale)
         return hip_ops.loss_sum(row_loss, scale)
-    return _InBatchXent.apply(q, c, logq, scale, ids)
+    return _InBatchXent.apply(q, c, logq, scale, ids, weights, float(weight_scale))
 
 
 class InBatchSoftmaxCrossEntropy:
@@ -405,8 +464,8 @@ class InBatchSoftmaxCrossEntropy:
             raise ValueError("the in-batch loss is defined on logits (from_logits=True)")
         self.reduction = str(reduction).lower().split(".")[-1]
 
-    def __call__(self, q, c, logq=None, ids=None):
-        return inbatch_softmax_xent(q, c, logq, self.reduction, ids)
+    def __call__(self, q, c, logq=None, ids=None, weights=None, weight_scale: float = 1.0):
+        return inbatch_softmax_xent(q, c, logq, self.reduction, ids, weights, weight_scale)
 
 
 # Name the reference compiles with.

@@ -37,11 +37,15 @@ from pkg.modelling.models.tower import Tower
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["TwoTowerModel", "GraphedTrainStep", "LOGQ_KEY"]
+__all__ = ["TwoTowerModel", "GraphedTrainStep", "LOGQ_KEY", "WEIGHT_KEY"]
 
 # Optional batch entry carrying per-example log p(candidate) computed from raw
 # ids at encoding time (exact even for ids outside a truncated vocab).
 LOGQ_KEY = "__logq__"
+# Optional batch entry making the batch a WEIGHTED one: per-example sample
+# weights, fp32 [B], normalised to [0, 1] (w / w_max; encode_dataframe's
+# sample_weight).  The model's sample_weight_scale holds w_max.
+WEIGHT_KEY = "__weight__"
 # each tower's dense (MLP) Adagrad step issued inside the backward on that
 # tower's stream the moment its weight gradient exists, instead of after the
 # join (the embedding update stays one call after the backward)
@@ -83,6 +87,12 @@ class TwoTowerModel(AbstractKerasModel):
         out-of-vocabulary candidates, id 0, count as one) is no negative of
         that row, in training and in evaluation — a departure from the
         reference's loss (TensorFlow Recommenders' remove_accidental_hits).
+    sample_weight_scale: float (attribute, default 1.0)
+        A batch carrying WEIGHT_KEY ("__weight__": fp32 [B] in [0, 1]) is a
+        weighted batch: its loss is sample_weight_scale * sum_i w_i l_i, in
+        training and in evaluation (Keras fit(sample_weight=...), with the
+        weights normalised by their maximum and the maximum kept here; fit
+        takes it from the dataset).  A batch without the key is unweighted.
     normalize_embeddings: bool
         Off (the default): scores are dot products of the towers' ReLU
         outputs, the reference's.  On: both towers' outputs are L2-normalised
@@ -115,6 +125,7 @@ class TwoTowerModel(AbstractKerasModel):
                                  "rescales the top layers)")
         self.temperature = temperature
         self.remove_accidental_hits = bool(remove_accidental_hits)
+        self.sample_weight_scale = 1.0
         # apply each tower's Adagrad step inside the backward (see train_step)
         self.fused_optimizer_apply = bool(fused_optimizer_apply)
         self.query_features = query_features
@@ -197,6 +208,17 @@ class TwoTowerModel(AbstractKerasModel):
         ids = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
         return ids.reshape(-1).to(self.device, torch.int32).contiguous()
 
+    def sample_weights(self, x: Dict[str, Any]) -> Optional[torch.Tensor]:
+        """The batch's normalised sample weights [B] (fp32, on the device), or
+        None for a batch without WEIGHT_KEY.  A view of the batch's column
+        when that is an fp32 device tensor already (the graphed step's static
+        word buffer): no copy, nothing to re-capture."""
+        if WEIGHT_KEY not in x:
+            return None
+        v = x[WEIGHT_KEY]
+        v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, np.float32))
+        return v.reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+
     def _logq_call(self, x: Dict[str, Any]):
         """(segments, out) of the logQ lookup as a 1-wide gather call, or None
         when logQ comes another way (precomputed in the batch / disabled)."""
@@ -236,23 +258,25 @@ class TwoTowerModel(AbstractKerasModel):
                     # the forward instead of landing in front of the backward
                     self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
             logq = call[1].view(-1) if call is not None else self.candidate_logq(x)
-            return self.tower_loss(qi, ci, logq, self.candidate_ids(x))
+            return self.tower_loss(qi, ci, logq, self.candidate_ids(x), self.sample_weights(x))
 
     def tower_loss(self, qi: torch.Tensor, ci: torch.Tensor, logq: Optional[torch.Tensor],
-                   ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   ids: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Loss from the gathered tower inputs: with gradients, both MLPs and the
         in-batch loss run as one autograd node (losses.towers_inbatch_softmax_xent).
-        ids: candidate_ids(x) (accidental hits removed), or None."""
+        ids: candidate_ids(x) (accidental hits removed), or None.  weights:
+        sample_weights(x), or None (an unweighted batch: the calls as ever)."""
+        wkw = {} if weights is None else {"weights": weights, "weight_scale": float(self.sample_weight_scale)}
         if torch.is_grad_enabled():
             return towers_inbatch_softmax_xent(qi, ci, self.query_tower.dense, self.candidate_tower.dense, logq,
                                                self.loss.reduction, getattr(self, "_on_tower", None),
-                                               getattr(self, "_on_dx", None), ids)
+                                               getattr(self, "_on_dx", None), ids, **wkw)
         sq, sc = self.query_tower.dense, self.candidate_tower.dense
         if sq.normalize or sc.normalize:  # both outputs normalised in one launch, after both towers
             q, c, _ = normalized_outputs(sq, sc, sq.forward_acts(qi, sq.flat.detach())[-1],
                                          sc.forward_acts(ci, sc.flat.detach())[-1])
-            return self.loss(q, c, logq, ids)
-        return self.loss(sq(qi), sc(ci), logq, ids)
+            return self.loss(q, c, logq, ids, **wkw)
+        return self.loss(sq(qi), sc(ci), logq, ids, **wkw)
 
     def compile(self, loss=None, optimizer=None, **kwargs) -> None:
         """Keras-style compile: the loss must be the in-batch softmax CE
@@ -370,6 +394,8 @@ class TwoTowerModel(AbstractKerasModel):
         (Keras' loss metric is the running mean over the epoch's batches)."""
         from pkg.modelling.dataset import DeviceDataset
 
+        if getattr(dataset, "weight_scale", None) is not None:  # w_max of the dataset's "__weight__" column
+            self.sample_weight_scale = float(dataset.weight_scale)
         if use_graph and isinstance(dataset, DeviceDataset) and dataset.fn is None and dataset.batch_size:
             return self._fit_device(dataset, epochs, callbacks)
         history: Dict[str, List[float]] = {"loss": []}
@@ -554,12 +580,23 @@ class GraphedTrainStep:
             self.out = self._step()
         # what the captured pointers refer to (see reusable)
         self.optimizer = model.optimizer
+        # a weighted step (rows, fold, cols, tt_sum) with w_max a constant of the graph
+        self.weight_scale = float(model.sample_weight_scale) if WEIGHT_KEY in self.static else None
         self.ws_snapshot = hip_ops.Workspace.snapshot(owner=self.graph)
 
-    def reusable(self, model: "TwoTowerModel", source=None) -> bool:
+    def reusable(self, model: "TwoTowerModel", source=None, batch: Optional[Dict[str, Any]] = None) -> bool:
         """True while a replay still trains `model` from `source` through the
         buffers it was captured with: same optimizer object (its slots), no
-        libtt workspace regrown or cleared since the capture."""
+        libtt workspace regrown or cleared since the capture.  Sample weights:
+        a graph captured without "__weight__" is refused for a source (or
+        `batch`) that carries it and the other way round, and so is one
+        captured with another sample_weight_scale."""
+        keys = source.float_keys if source is not None else batch
+        weighted = self.weight_scale is not None
+        if keys is not None and (WEIGHT_KEY in keys) != weighted:
+            return False
+        if weighted and self.weight_scale != float(model.sample_weight_scale):
+            return False
         return (self.model is model and self.source is source and self.optimizer is model.optimizer
                 and (source is None or int(source.batch_size) == self.batch_size)
                 and hip_ops.Workspace.unchanged(self.ws_snapshot))
@@ -592,13 +629,24 @@ class GraphedTrainStep:
 
     def pack(self, batch: Dict[str, Any]):
         """Device buffers laid out like the static batch (copy with one D2D each)."""
+        self._check_keys(batch)
         ib = torch.cat([self._int_rows(k, self._to_dev(batch[k], self.model.device))
                         for k in self.int_keys]) if self.int_keys else self._ibuf.clone()
         fb = torch.stack([self._to_dev(batch[k], self.model.device).reshape(-1).to(torch.float32)
                           for k in self.float_keys]) if self.float_keys else self._fbuf.clone()
         return ib.contiguous(), fb.contiguous()
 
+    def _check_keys(self, batch: Dict[str, Any]) -> None:
+        """A step captured with sample weights takes weighted batches only, one
+        captured without them unweighted ones only (the graph holds one or the
+        other chain of launches)."""
+        if (WEIGHT_KEY in batch) != (WEIGHT_KEY in self.static):
+            raise ValueError(f"this step was captured {'with' if WEIGHT_KEY in self.static else 'without'} "
+                             f"{WEIGHT_KEY}; the batch comes {'with' if WEIGHT_KEY in batch else 'without'} it "
+                             "(capture another GraphedTrainStep)")
+
     def load(self, batch: Dict[str, Any]) -> None:
+        self._check_keys(batch)
         for k, v in batch.items():
             self.static[k].copy_(self._to_dev(v, self.model.device).reshape(self.static[k].shape), non_blocking=True)
 

@@ -971,6 +971,48 @@ typedef struct {
 } tt_bag_grad_job;
 int tt_bag_grad_expand(const tt_bag_grad_job* jobs, int32_t num_jobs, int64_t batch, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Per-example sample weights of the in-batch loss (TensorFlow Recommenders'
+ * Retrieval task sample_weight, Keras fit(sample_weight=...); the reference
+ * has no such option):  L = sum_i w_i l_i.  ONE launch between the rows pass
+ * and the cols pass; no pass kernel changes.  w [n] holds the NORMALISED
+ * weights w_i / w_max in [0, 1]; the loss is linear in w, so the caller puts
+ * w_max into the loss scale and the backward's scalar.
+ *
+ * The cols entries use lse and row_loss only in exp(S'_ij - lse_i) (negative
+ * pairs) and in -expm1(-row_loss_i) = 1 - P_ii (the positive pair).  Handed
+ *   lse_w_i      = lse_i - ln w_i                       and
+ *   row_loss_w_i = -log1p(w_i expm1(-row_loss_i)),  so that
+ *   -expm1(-row_loss_w_i) = w_i (1 - P_ii),
+ * the unchanged cols entry returns sum_{i != r} w_i P_ij q_i - w_r (1 - P_rr)
+ * q_r, the weighted loss's gradient.  d L / d q_i is the rows pass's dq row
+ * scaled by w_i, done here in place.  Per row i:
+ *   w_i == 1:     wloss = row_loss_i, lse_w = lse_i, row_loss_w = row_loss_i
+ *                 (the same bits: copies, not the formulas); dq row not touched.
+ *   w_i == 0:     wloss = +0, lse_w = +inf, row_loss_w = +0; dq row STORED as
+ *                 +0 (not multiplied: an inf or NaN in it does not survive).
+ *   0 < w_i < 1:  wloss = w_i * row_loss_i (one IEEE multiply),
+ *                 lse_w = lse_i - logf(w_i),
+ *                 row_loss_w = -log1pf(w_i * expm1f(-row_loss_i)),
+ *                 dq[i, e] = w_i * dq[i, e] (one IEEE multiply per element).
+ *   w_i < 0, w_i > 1 or NaN: NaN in all three scalars and in the dq row (the
+ *                 loss goes NaN in sight; no silent clamp).
+ * dq [n, lddq] may be NULL (and is not looked at when dim == 0: the
+ * evaluation loss); wloss may be NULL; lse_w / row_loss_w may alias lse /
+ * row_loss (each row's scalars are read before they are written, by one
+ * lane).  dq rows need not be 16-byte aligned: 16-byte accesses are used
+ * only where dq's base is 16-byte aligned and lddq is a multiple of 4, with
+ * the same result bits.  Columns dim..lddq are never written.  A row's
+ * results depend only on that row's inputs.  Stream-ordered, no workspace,
+ * no allocation, no synchronisation, no atomics; n is not bounded by the
+ * grid.  n == 0: TT_OK, no work (the pointers are not looked at).
+ * TT_ERR_BAD_ARG (with a message, checked on the host before the launch):
+ * n < 0, dim < 0, lddq < dim, or (n > 0) NULL w, lse, row_loss, lse_w or
+ * row_loss_w. */
+int tt_inbatch_weight_rows(const float* w, const float* lse, const float* row_loss, int64_t n,
+                           float* lse_w, float* row_loss_w, float* wloss,
+                           float* dq, int64_t lddq, int32_t dim, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
