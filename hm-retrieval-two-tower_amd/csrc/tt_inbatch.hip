@@ -174,6 +174,8 @@ struct PassArgs {
   const __bf16* strm_lo;
   const int32_t* stat_ids;  // hits mode: [n_stat_pad] / [n_strm_pad] candidate ids
   const int32_t* strm_ids;
+  const float* thr;         // hard mode: the rows' thresholds, [n_stat_pad] (rows pass) / [n_strm_pad] (cols pass)
+  const float* stat_bias;   // hard mode, cols pass: [n_stat_pad] -logq of the stationary columns
 };
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -258,15 +260,41 @@ __device__ __forceinline__ void wait_vmcnt() {
 // (the X3 form has no register to keep one in).  The positive pair matches
 // by id as a rule but need not (the entries take any ids): mask_diag stays,
 // so it is excluded from the sums however the ids are filled.
-template <int D, int MODE, bool X3 = false, bool HITS = false>
-__global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(const PassArgs a) {
+//
+// HARD (opt-in, the tt_inbatch_*_hard entries): hard-negative mining.  A
+// score below its ROW's threshold (hard_select_kernel below) becomes -inf
+// after the score MFMAs, so p = 0 exactly like a masked hit.  Rows pass: the
+// row is the stationary one; the wave's 32 thresholds sit in LDS beside the
+// stationary ids and one is read per tile; the compare sits in front of the
+// exp2 of region A.  (The running max still reads the unmasked scores: a
+// row's largest negative is always kept, so it is the kept set's max too.)
+// Cols pass: the row is the streamed one; the tile's 64 thresholds ride the
+// ring in a slot of their own (one more dma_b32 of wave 0).  This pass's own
+// scores start from -lse_i, not from -logq_j, so they are not S': the tile's
+// S' is formed first, into the registers that then receive the pass's scores,
+// from the rows pass's sequence — accumulator -logq_j (this lane's column),
+// then per k-step the same products in the same order (x3: hi.hi, then the
+// rows pass's hi.lo, which is this pass's lo.hi, then its lo.hi), so it is the
+// rows pass's and the selection's S' bit for bit in both arithmetics — and
+// compared with the thresholds (one ds_read_b128 per four scores) into one
+// bit per score.  The pass's scores are then formed exactly as without HARD
+// and the flagged ones set to -inf in the second half of region B, whose
+// VALU share is empty in this pass.  The score MFMAs of this pass double.
+template <int D, int MODE, bool X3 = false, bool HITS = false, bool HARD = false>
+__global__ void __launch_bounds__(kThreads, (X3 || (HARD && MODE == 1 && D == 128)) ? 1 : 2)
+    inbatch_pass_kernel(const PassArgs a) {
+  // (HARD cols pass at D = 128: 7 registers over 256 with the second score
+  // chain, so one workgroup per CU as X3; every other bf16 form keeps two)
   using G = Geo<D>;
   constexpr int IMG = X3 ? 2 : 1;                           // bf16 images per streamed tile
   constexpr int LO_OFF = kRingStages * G::A_BYTES;          // the lo ring (X3)
   constexpr int BIAS_OFF = IMG * kRingStages * G::A_BYTES;
   constexpr int IDS_OFF = BIAS_OFF + kRingStages * kTile * 4;  // HITS: kRingStages x 64 streamed ids,
   constexpr int SID_OFF = IDS_OFF + kRingStages * kTile * 4;   // then the workgroup's 128 stationary ids
-  constexpr int BDMA = HITS ? 2 : 1;                        // wave 0's 4-byte DMAs per tile
+  // HARD: kRingStages x 64 streamed thresholds (cols pass) / the workgroup's 128 (rows pass)
+  constexpr int THR_OFF = BIAS_OFF + kRingStages * kTile * 4 + (HITS ? (kRingStages * kTile + kRowsPerWG) * 4 : 0);
+  constexpr bool HARD_S = HARD && MODE == 1;                // thresholds streamed with the tile
+  constexpr int BDMA = 1 + (HITS ? 1 : 0) + (HARD_S ? 1 : 0);  // wave 0's 4-byte DMAs per tile
   extern __shared__ __attribute__((aligned(16))) char ring[];
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
   const int lane = lane_id();
@@ -298,12 +326,20 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
   const i32x4 ldesc = buffer_desc(X3 ? a.strm_lo : a.strm, static_cast<unsigned>(a.n_strm_pad * D * 2));
   const i32x4 idesc = buffer_desc(HITS ? static_cast<const void*>(a.strm_ids) : a.bias,
                                   static_cast<unsigned>(a.n_strm_pad * 4));
+  const i32x4 tdesc = buffer_desc(HARD_S ? static_cast<const void*>(a.thr) : a.bias,
+                                  static_cast<unsigned>(a.n_strm_pad * 4));
   if constexpr (HITS) {
     // a wave reads back only what its own lanes wrote (LDS ops of a wave
     // complete in order): no barrier
     if (h == 0)
       *reinterpret_cast<volatile int*>(ring + SID_OFF + (wave * kRowsPerWave + l32) * 4) = a.stat_ids[stat_row];
   }
+  if constexpr (HARD && MODE == 0) {  // as the stationary ids
+    if (h == 0)
+      *reinterpret_cast<volatile float*>(ring + THR_OFF + (wave * kRowsPerWave + l32) * 4) = a.thr[stat_row];
+  }
+  float sbias = 0.0f;  // HARD, cols pass: -logq of this lane's column
+  if constexpr (HARD_S) sbias = a.stat_bias[stat_row];
   unsigned voff[G::PPW];
 #pragma unroll
   for (int u = 0; u < G::PPW; ++u) {
@@ -328,6 +364,7 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
     if (wave == 0) {
       dma_b32(bdesc, lane * 4, row0 * 4, ring_lds + BIAS_OFF + stage * (kTile * 4));
       if constexpr (HITS) dma_b32(idesc, lane * 4, row0 * 4, ring_lds + IDS_OFF + stage * (kTile * 4));
+      if constexpr (HARD_S) dma_b32(tdesc, lane * 4, row0 * 4, ring_lds + THR_OFF + stage * (kTile * 4));
     }
   };
   // Wait until at most `ahead` issued tiles of this wave are still in flight.
@@ -460,6 +497,70 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
       sacc[k >> 4][k & 15] = kd == k ? -INFINITY : sacc[k >> 4][k & 15];
   };
 
+  // HARD, cols pass: the thresholds of scores [k0, k0 + 4) of a lane (streamed
+  // rows 32(k0>>4) + 8((k0&15)>>2) + 4h + 0..3 of the tile in `stage`), and
+  // the scores below them out.
+  auto rd_thr4 = [&](int stage, int k0) {
+    return *reinterpret_cast<const f32x4*>(ring + THR_OFF + stage * (kTile * 4) +
+                                           (4 * h + 32 * (k0 >> 4) + 8 * ((k0 & 15) >> 2)) * 4);
+  };
+  // bit k: S' of score k of the tile in `stage` is below its row's threshold
+  auto drop_bits = [&](int stage, f32x16* s) {  // s: scratch, the registers the tile's scores go to next
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[t][r] = sbias;
+    // The fragment reads go through a copy of the lane's base offset that the
+    // compiler cannot see through: read as rd_a, they would be merged with
+    // region A's reads of the same stage and every fragment of the tile kept
+    // in registers from here to there.  One read ahead of its MFMAs, pinned.
+    auto rd2 = [&](int i, int img_off) {
+      int rb = rbase[i >> 1];
+      asm volatile("" : "+v"(rb));
+      return *reinterpret_cast<const bf16x8*>(ring + rb + (img_off + stage * G::A_BYTES + (i & 1) * 32 * 2 * D));
+    };
+    bf16x8 nh = rd2(0, 0), nl = nh;
+    if constexpr (X3) nl = rd2(0, LO_OFF);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 2 * G::KS; ++i) {
+      const bf16x8 ah = nh, al = nl;
+      if (i + 1 < 2 * G::KS) {
+        nh = rd2(i + 1, 0);
+        if constexpr (X3) nl = rd2(i + 1, LO_OFF);
+      }
+      s[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bfrag[i >> 1], s[i & 1], 0, 0, 0);
+      if constexpr (X3) {
+        s[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bfrag[i >> 1], s[i & 1], 0, 0, 0);
+        s[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bfrag_lo[i >> 1], s[i & 1], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // shifted in from score 31 down (bit k = score k); the empty asm keeps the
+    // shift-and-or form (folded, it needs the 32 constants 1 << k in registers)
+    unsigned bits = 0u;
+#pragma unroll
+    for (int k0 = 28; k0 >= 0; k0 -= 4) {
+      const f32x4 t4 = rd_thr4(stage, k0);
+#pragma unroll
+      for (int u = 3; u >= 0; --u) {
+        bits = (bits << 1) | (s[(k0 + u) >> 4][(k0 + u) & 15] < t4[u] ? 1u : 0u);
+        asm volatile("" : "+v"(bits));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    return bits;
+  };
+  auto mask_bits = [&](f32x16* sacc, unsigned bits, int k0, int k1) {
+    unsigned b = bits >> k0;
+#pragma unroll
+    for (int k = k0; k < k1; ++k) {
+      asm volatile("" : "+v"(b));  // (as above: no per-bit constants)
+      sacc[k >> 4][k & 15] = (b & 1u) ? -INFINITY : sacc[k >> 4][k & 15];
+      b >>= 1;
+    }
+  };
+
   const int pre = ntiles < kRingStages ? ntiles : kRingStages;
   for (int t = 0; t < pre; ++t) issue(t);
   f32x16 sa[2], sb[2];
@@ -467,8 +568,11 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
   if (ntiles > 0) {
     wait_tiles(pre - 1);  // tile 0 landed
     __builtin_amdgcn_s_barrier();
+    unsigned drop0 = 0u;
+    if constexpr (HARD_S) drop0 = drop_bits(0, sa);
     scores_plain(sa);
     mask_diag(sa, 0);
+    if constexpr (HARD_S) mask_bits(sa, drop0, 0, 32);
     if constexpr (MODE == 0) mx = half_max(sa);
   }
 
@@ -521,7 +625,12 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
         else fr[idx % FR] = rd_t(STG, k);
       }
     };
+    unsigned drop = 0u;  // HARD, cols pass: S(tile+1)'s scores below their rows' thresholds
+    if constexpr (HARD_S) drop = drop_bits(NXT, sn);
     rd_bias(NXT, sn);
+    float thr_row = -INFINITY;  // HARD, rows pass: this lane's row's threshold
+    if constexpr (HARD && MODE == 0)
+      thr_row = *reinterpret_cast<const volatile float*>(ring + THR_OFF + (wave * kRowsPerWave + l32) * 4);
 #pragma unroll
     for (int i = 0; i < AHEAD; ++i) prefetch(i);
     const float mb = (MODE == 0) ? m_run : 0.0f;
@@ -541,6 +650,8 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
       }
 #pragma unroll
       for (int k = i * EPS; k < (i + 1) * EPS; ++k) {
+        if constexpr (HARD && MODE == 0)
+          sc[k >> 4][k & 15] = sc[k >> 4][k & 15] < thr_row ? -INFINITY : sc[k >> 4][k & 15];
         sc[k >> 4][k & 15] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[k >> 4][k & 15], kLog2e, -mb));
         if ((k & 7) == 7) {
           const int g = k >> 3, t = g >> 1, b = 8 * (g & 1);
@@ -584,6 +695,9 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
       // by now (masked right after region A the wave waited for them: +4 %
       // per pass), and the next max below reads them after
       if (j == MX0) mask_diag(sn, tile + 1);
+      if constexpr (HARD_S) {
+        if (j >= MX0) mask_bits(sn, drop, (j - MX0) * EMX, (j - MX0 + 1) * EMX);
+      }
       if constexpr (MODE == 0) {
 #pragma unroll
         for (int k = j * EPP; k < (j + 1) * EPP; ++k) l_run += sc[k >> 4][k & 15];
@@ -636,6 +750,208 @@ __global__ void __launch_bounds__(kThreads, X3 ? 1 : 2) inbatch_pass_kernel(cons
       for (int u = 0; u < 4; ++u) v[u] = o[dt][4 * r4 + u];
       *reinterpret_cast<f32x4*>(po + 32 * dt + 8 * r4 + 4 * h) = v;
     }
+}
+
+// ---------------------------------------------------------------------------
+// Hard-negative selection: thr[i] of include/tt.h (tt_inbatch_hard_threshold)
+// for every stationary row, exactly, in one launch.
+//
+// A workgroup owns 32 stationary rows; its 4 waves hold the same B fragments
+// and take the streamed 64-row tiles round robin.  Scores come from the rows
+// pass's MFMA sequence (accumulator = bias or -inf for a hit, then per k-step
+// hi.hi [, hi.lo, lo.hi]), so S' is the rows pass's bit for bit; an MFMA
+// output element depends on its own operand rows only, not on where the
+// fragment came from, so the streamed fragments are read straight from global
+// memory (no LDS ring: every wave re-reads its tiles from the L2-resident
+// image, which is what the five sweeps cost — DESIGN.md §4 "Hard negatives").
+// Radix select on the order-preserving uint32 key of S', 8-bit digits from
+// the top: each of the 4 rounds re-streams the columns, counts the digit of
+// the keys that share the row's prefix into the row's 256-bin LDS histogram
+// (integer atomics: exact whatever the order), and 32 threads walk their
+// row's bins from the top to the bin holding rank K.  Row stride 257 words:
+// the 32 rows of one atomic instruction hit 32 banks even when every key
+// falls into one bin (the sign / exponent digit of round 0), and the two
+// lanes of a row (h = 0, 1) are its only same-address pair.  After round 3
+// the prefix is a's key; b = a when the last bin holds rank K + 1 too, else
+// one more sweep takes the largest key below a (a register max per lane, one
+// LDS atomic max at the end).  -inf scores (hits, padded columns, the
+// positive) are not counted: with F finite negatives, F <= K is exactly
+// "at most K negatives, or b = -inf" and gives thr = -inf; with F > K both a
+// and b are finite.
+constexpr int kSelRows = 32;                  // stationary rows per workgroup
+constexpr int kSelStride = 257;               // histogram row stride (words)
+constexpr unsigned kKeyNegInf = 0x007fffffu;  // score_key(-inf)
+
+__device__ __forceinline__ unsigned score_key(float x) {
+  const unsigned u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+struct SelectArgs {
+  const __bf16* stat;     // as PassArgs of the rows pass
+  const __bf16* strm;
+  const float* bias;
+  int64_t n_stat;         // rows of thr
+  int64_t n_strm_pad;
+  int64_t diag_off;
+  const __bf16* stat_lo;
+  const __bf16* strm_lo;
+  const int32_t* stat_ids;
+  const int32_t* strm_ids;
+  unsigned k;             // >= 1
+  float* thr;             // [n_stat]
+  float* thr_pad;         // [n_stat_pad] with -inf past n_stat, or NULL
+};
+
+template <int D, bool X3, bool HITS>
+__global__ void __launch_bounds__(kThreads) hard_select_kernel(const SelectArgs a) {
+  using G = Geo<D>;
+  __shared__ unsigned hist[kSelRows * kSelStride];
+  __shared__ unsigned s_prefix[kSelRows];  // the key digits fixed so far
+  __shared__ unsigned s_want[kSelRows];    // rank still to find inside the prefix (0: thr = -inf)
+  __shared__ unsigned s_below[kSelRows];   // b's key
+  __shared__ int s_sweep;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+  const int lane = lane_id();
+  const int h = lane >> 5;
+  const int l32 = lane & 31;
+  const int64_t stat_row = static_cast<int64_t>(blockIdx.x) * kSelRows + l32;
+  const int ntiles = static_cast<int>(a.n_strm_pad / kTile);
+
+  bf16x8 bfrag[G::KS];
+  bf16x8 bfrag_lo[X3 ? G::KS : 1];
+#pragma unroll
+  for (int s = 0; s < G::KS; ++s) {
+    bfrag[s] = *reinterpret_cast<const bf16x8*>(a.stat + stat_row * D + 16 * s + 8 * h);
+    if constexpr (X3) bfrag_lo[s] = *reinterpret_cast<const bf16x8*>(a.stat_lo + stat_row * D + 16 * s + 8 * h);
+  }
+  int sid = 0;
+  if constexpr (HITS) sid = a.stat_ids[stat_row];
+  const int64_t dpos = stat_row + a.diag_off;  // the positive's streamed row
+
+  // The tile's 32 keys of this lane (score k: streamed row 32(k>>4) +
+  // 8((k&15)>>2) + 4h + (k&3), as in the pass); the positive's is kKeyNegInf.
+  auto tile_keys = [&](int tile, unsigned* key) {
+    const int64_t row0 = static_cast<int64_t>(tile) * kTile;
+    f32x16 sacc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const int64_t r = row0 + 32 * t + 8 * r4 + 4 * h;
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + r);
+        if constexpr (HITS) {
+          const i32x4 id4 = *reinterpret_cast<const i32x4*>(a.strm_ids + r);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sacc[t][4 * r4 + u] = id4[u] == sid ? -INFINITY : b4[u];
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sacc[t][4 * r4 + u] = b4[u];
+        }
+      }
+#pragma unroll
+    for (int i = 0; i < 2 * G::KS; ++i) {
+      const int64_t off = (row0 + 32 * (i & 1) + l32) * D + 16 * (i >> 1) + 8 * h;
+      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a.strm + off);
+      sacc[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bfrag[i >> 1], sacc[i & 1], 0, 0, 0);
+      if constexpr (X3) {
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(a.strm_lo + off);
+        sacc[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bfrag_lo[i >> 1], sacc[i & 1], 0, 0, 0);
+        sacc[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bfrag[i >> 1], sacc[i & 1], 0, 0, 0);
+      }
+    }
+    const int64_t d64 = dpos - row0;
+    const int d = (d64 >= 0 && d64 < kTile) ? static_cast<int>(d64) : -1;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      const int r = 32 * (k >> 4) + 8 * ((k & 15) >> 2) + 4 * h + (k & 3);
+      key[k] = r == d ? kKeyNegInf : score_key(sacc[k >> 4][k & 15]);
+    }
+  };
+
+  unsigned* myhist = hist + l32 * kSelStride;
+  for (int round = 0; round < 4; ++round) {
+    const int shift = 24 - 8 * round;
+    for (int i = threadIdx.x; i < kSelRows * kSelStride; i += kThreads) hist[i] = 0u;
+    __syncthreads();  // (also: the previous round's s_prefix / s_want are written)
+    const unsigned pfx = round ? s_prefix[l32] : 0u;
+    const bool live = round == 0 || s_want[l32] != 0u;
+    for (int tile = wave; tile < ntiles; tile += kWavesPerWG) {
+      unsigned key[32];
+      tile_keys(tile, key);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) {
+        // round 0 counts every finite score; later rounds those inside the prefix
+        const bool in = key[k] != kKeyNegInf && live && (round == 0 || ((key[k] ^ pfx) >> (shift + 8)) == 0u);
+        if (in) atomicAdd(myhist + ((key[k] >> shift) & 255u), 1u);
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < kSelRows) {
+      const unsigned* hrow = hist + threadIdx.x * kSelStride;
+      unsigned want = round ? s_want[threadIdx.x] : a.k;
+      if (round == 0) {
+        unsigned total = 0u;
+        for (int bin = 0; bin < 256; ++bin) total += hrow[bin];
+        if (total <= a.k) want = 0u;  // F <= K
+        s_prefix[threadIdx.x] = 0u;
+      }
+      if (want != 0u) {
+        unsigned above = 0u, cnt = 0u;
+        int bin = 255;
+        for (; bin > 0; --bin) {
+          cnt = hrow[bin];
+          if (above + cnt >= want) break;
+          above += cnt;
+        }
+        if (bin == 0) cnt = hrow[0];
+        s_prefix[threadIdx.x] |= static_cast<unsigned>(bin) << shift;
+        want -= above;  // a's rank inside the bin, 1-based
+        if (round == 3) s_below[threadIdx.x] = want + 1u <= cnt ? s_prefix[threadIdx.x] : 0u;  // b = a : swept
+      }
+      s_want[threadIdx.x] = want;
+    }
+    __syncthreads();  // the walk is done before the bins are cleared again
+  }
+  if (threadIdx.x == 0) s_sweep = 0;
+  __syncthreads();
+  if (threadIdx.x < kSelRows && s_want[threadIdx.x] != 0u && s_below[threadIdx.x] == 0u) s_sweep = 1;
+  __syncthreads();
+  if (s_sweep) {  // workgroup-uniform
+    const unsigned ka = s_prefix[l32];
+    const bool need = s_want[l32] != 0u && s_below[l32] == 0u;
+    unsigned best = 0u;
+    for (int tile = wave; tile < ntiles; tile += kWavesPerWG) {
+      unsigned key[32];
+      tile_keys(tile, key);
+#pragma unroll
+      for (int k = 0; k < 32; ++k)
+        if (key[k] != kKeyNegInf && key[k] < ka && key[k] > best) best = key[k];
+    }
+    if (need && best != 0u) atomicMax(s_below + l32, best);
+    __syncthreads();
+  }
+  if (threadIdx.x < kSelRows) {
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * kSelRows + threadIdx.x;
+    float t = -INFINITY;
+    if (s_want[threadIdx.x] != 0u) {
+      const float va = key_score(s_prefix[threadIdx.x]), vb = key_score(s_below[threadIdx.x]);
+      t = 0.5f * va + 0.5f * vb;   // both halves exact: one rounding
+      if (va > vb && t == vb) t = va;  // the midpoint must not admit b
+    }
+    if (row < a.n_stat) a.thr[row] = t;
+    if (a.thr_pad) a.thr_pad[row] = row < a.n_stat ? t : -INFINITY;
+  }
+}
+
+// thr [n] -> dst [n_pad], -inf past n (the padded rows the passes read).
+__global__ void __launch_bounds__(256) pad_thr_kernel(const float* __restrict__ thr, int64_t n,
+                                                      float* __restrict__ dst, int64_t n_pad) {
+  const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+  if (i < n_pad) dst[i] = i < n ? thr[i] : -INFINITY;
 }
 
 // Split combines: D/4 lanes per row (float4 partials), 1024/D rows per block.
@@ -920,9 +1236,11 @@ struct PassWs {
   float* part_l;
   float* part_o;
   int32_t *stat_ids, *strm_ids;  // hits mode only
+  float* thr;                    // hard mode only: the rows' thresholds, padded,
+  float* stat_bias;              // and (cols pass) the stationary columns' -logq
 };
 
-PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false) {
+PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false, bool hard = false) {
   PassWs w;
   w.stat = cv.take<__bf16>(p.stat_pad * p.D);
   w.strm = cv.take<__bf16>(p.strm_pad * p.D);
@@ -935,12 +1253,14 @@ PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false)
   // after everything else: the plain entries' carve does not move
   w.stat_ids = hits ? cv.take<int32_t>(p.stat_pad) : nullptr;
   w.strm_ids = hits ? cv.take<int32_t>(p.strm_pad) : nullptr;
+  w.thr = hard ? cv.take<float>(p.stat_pad > p.strm_pad ? p.stat_pad : p.strm_pad) : nullptr;
+  w.stat_bias = hard ? cv.take<float>(p.stat_pad) : nullptr;
   return w;
 }
 
-size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false, bool hits = false) {
+size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false, bool hits = false, bool hard = false) {
   Carver cv(nullptr, 0);
-  carve_pass(cv, make_plan(n_stat, n_strm, dim), x3, hits);
+  carve_pass(cv, make_plan(n_stat, n_strm, dim), x3, hits, hard);
   return cv.used();
 }
 
@@ -1004,14 +1324,15 @@ int combine_cols(int D, hipStream_t st, const float* po, int nsplit, int64_t n_s
   return TT_OK;
 }
 
-template <int D, int MODE, bool X3, bool HITS>
+template <int D, int MODE, bool X3, bool HITS, bool HARD>
 int launch_pass_d(dim3 grid, const PassArgs& a, hipStream_t st) {
-  // HITS: the streamed ids' ring slot and the workgroup's stationary ids
+  // HITS: the streamed ids' ring slot and the workgroup's stationary ids;
+  // HARD: the thresholds' ring slot (cols pass) / the workgroup's 128 (rows pass)
   constexpr int shm = Geo<D>::LDS_BYTES + (X3 ? kRingStages * Geo<D>::A_BYTES : 0) +
-                      (HITS ? (kRingStages * kTile + kRowsPerWG) * 4 : 0);
+                      (HITS ? (kRingStages * kTile + kRowsPerWG) * 4 : 0) + (HARD ? kRingStages * kTile * 4 : 0);
   if (shm > 65536) {
     static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(inbatch_pass_kernel<D, MODE, X3, HITS>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(inbatch_pass_kernel<D, MODE, X3, HITS, HARD>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, shm);
     TT_CHECK_HIP(attr);
   }
@@ -1019,31 +1340,65 @@ int launch_pass_d(dim3 grid, const PassArgs& a, hipStream_t st) {
   const int reps = probe_reps(probe);  // > 1 only for a repeat probe (the pass is idempotent)
   probe_begin(probe, st);
   for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL((inbatch_pass_kernel<D, MODE, X3, HITS>), grid, dim3(kThreads), shm, st, a);
+    hipLaunchKernelGGL((inbatch_pass_kernel<D, MODE, X3, HITS, HARD>), grid, dim3(kThreads), shm, st, a);
   probe_end(MODE == 0 ? TT_PROBE_INBATCH_ROWS : TT_PROBE_INBATCH_COLS, st);
   TT_CHECK_LAUNCH();
   return TT_OK;
 }
 
-template <int MODE, bool X3 = false, bool HITS = false>
+template <int MODE, bool X3 = false, bool HITS = false, bool HARD = false>
 int launch_pass(const Plan& p, const PassArgs& a, hipStream_t st) {
   // buffer descriptors address the bf16 images with 32-bit byte offsets
   if (p.strm_pad * p.D * 2 >= (1ll << 31))
     return fail(TT_ERR_UNSUPPORTED, "inbatch: %lld x %d streamed batch too large", (long long)p.strm_pad, p.D);
   dim3 grid(static_cast<unsigned>(p.stat_pad / kRowsPerWG), static_cast<unsigned>(p.split));
   switch (p.D) {
-    case 32: return launch_pass_d<32, MODE, X3, HITS>(grid, a, st);
-    case 64: return launch_pass_d<64, MODE, X3, HITS>(grid, a, st);
-    default: return launch_pass_d<128, MODE, X3, HITS>(grid, a, st);
+    case 32: return launch_pass_d<32, MODE, X3, HITS, HARD>(grid, a, st);
+    case 64: return launch_pass_d<64, MODE, X3, HITS, HARD>(grid, a, st);
+    default: return launch_pass_d<128, MODE, X3, HITS, HARD>(grid, a, st);
   }
 }
 
-// a.stat_ids != NULL: the accidental-hit form of the pass
+// a.stat_ids != NULL: the accidental-hit form of the pass; a.thr != NULL: the
+// hard-negative form
 template <int MODE>
 int launch_pass_any(const Plan& p, const PassArgs& a, bool x3, hipStream_t st) {
+  if (a.thr) {
+    if (a.stat_ids)
+      return x3 ? launch_pass<MODE, true, true, true>(p, a, st) : launch_pass<MODE, false, true, true>(p, a, st);
+    return x3 ? launch_pass<MODE, true, false, true>(p, a, st) : launch_pass<MODE, false, false, true>(p, a, st);
+  }
   if (a.stat_ids) return x3 ? launch_pass<MODE, true, true>(p, a, st) : launch_pass<MODE, false, true>(p, a, st);
   return x3 ? launch_pass<MODE, true>(p, a, st) : launch_pass<MODE>(p, a, st);
 }
+
+template <bool X3, bool HITS>
+int launch_select_d(int D, dim3 grid, const SelectArgs& a, hipStream_t st) {
+  switch (D) {
+    case 32: hipLaunchKernelGGL((hard_select_kernel<32, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((hard_select_kernel<64, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
+    default: hipLaunchKernelGGL((hard_select_kernel<128, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
+  }
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+// The selection launch over the rows pass's prepared operands (a.stat_ids !=
+// NULL: with accidental hits at -inf).
+int launch_select(int D, int64_t stat_pad, const SelectArgs& a, bool x3, hipStream_t st) {
+  const dim3 grid(static_cast<unsigned>(stat_pad / kSelRows));
+  if (a.stat_ids) return x3 ? launch_select_d<true, true>(D, grid, a, st) : launch_select_d<false, true>(D, grid, a, st);
+  return x3 ? launch_select_d<true, false>(D, grid, a, st) : launch_select_d<false, false>(D, grid, a, st);
+}
+
+int pad_thr(const float* thr, int64_t n, float* dst, int64_t n_pad, hipStream_t st) {
+  hipLaunchKernelGGL(pad_thr_kernel, dim3(static_cast<unsigned>(ceil_div(n_pad, 256))), dim3(256), 0, st, thr, n, dst,
+                     n_pad);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+unsigned clamp_k(int64_t k) { return static_cast<unsigned>(k < (1ll << 31) ? k : (1ll << 31) - 1); }
 
 int check_common(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc, int64_t n_cols,
                  int32_t dim) {
@@ -1063,10 +1418,10 @@ using namespace tt;
 
 namespace tt {
 namespace {
-size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, bool hits = false) {
+size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, bool hits = false, bool hard = false) {
   if (n_rows < 1 || n_cols < 1 || pick_dpad(dim) == 0) return 0;
-  const size_t a = pass_bytes(n_rows, n_cols, dim, x3, hits);
-  const size_t b = pass_bytes(n_cols, n_rows, dim, x3, hits);
+  const size_t a = pass_bytes(n_rows, n_cols, dim, x3, hits, hard);
+  const size_t b = pass_bytes(n_cols, n_rows, dim, x3, hits, hard);
   return a > b ? a : b;
 }
 
@@ -1076,19 +1431,21 @@ size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, boo
 int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
               int64_t n_rows, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
               int64_t pos_offset, float* lse, float* row_loss, float* dq, void* workspace, size_t workspace_bytes,
-              tt_stream_t stream) {
+              tt_stream_t stream, bool hard = false, const float* thr = nullptr) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && row_loss, "%s: NULL lse/row_loss", fn);
+  TT_REQUIRE(!hard || thr, "%s: NULL thr", fn);
   TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
              "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
   const Plan p = make_plan(n_rows, n_cols, dim);
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr);
+  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr, hard);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
   const PrepJob none{};
+  if (hard && (rc = pad_thr(thr, n_rows, w.thr, p.stat_pad, st))) return rc;
   PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
   jq.dst_lo = w.stat_lo;
   jc.dst_lo = w.strm_lo;
@@ -1097,7 +1454,7 @@ int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* co
   if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
   if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, w.part_m, w.part_l, w.part_o,
-             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids};
+             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids, w.thr, nullptr};
   if ((rc = launch_pass_any<0>(p, a, x3, st))) return rc;
   return combine_rows(p.D, st, w.part_m, w.part_l, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, logq, n_rows, dim,
                       pos_offset, lse, row_loss, dq, nullptr);
@@ -1106,20 +1463,23 @@ int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* co
 int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
               int64_t n_rows, const float* lse, const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
               int32_t dim, const float* logq, int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes,
-              tt_stream_t stream) {
+              tt_stream_t stream, bool hard = false, const float* thr = nullptr) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && dc, "%s: NULL lse/dc", fn);
+  TT_REQUIRE(!hard || thr, "%s: NULL thr", fn);
   TT_REQUIRE(pos_offset >= 0 && n_cols + pos_offset <= n_rows,
              "%s: positives [pos_offset, pos_offset+n_cols) exceed n_rows", fn);
   const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr);
+  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr, hard);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
   const PrepJob none{};
+  if (hard && (rc = pad_thr(thr, n_rows, w.thr, p.strm_pad, st))) return rc;
   PrepJob jc = prep_job(c, ldc, n_cols, dim, w.stat), jq = prep_job(q, ldq, n_rows, dim, w.strm, lse, w.bias);
+  if (hard) jc.bv = logq, jc.bias = w.stat_bias;  // -logq of the stationary columns (-inf on padded ones)
   jc.dst_lo = w.stat_lo;
   jq.dst_lo = w.strm_lo;
   jc.ids = col_ids, jc.ids_dst = w.stat_ids;
@@ -1127,7 +1487,7 @@ int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* co
   if ((rc = prep(p.D, jc, none, dim, p.stat_pad, st))) return rc;
   if ((rc = prep(p.D, jq, none, dim, p.strm_pad, st))) return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o,
-             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids};
+             w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids, w.thr, w.stat_bias};
   if ((rc = launch_pass_any<1>(p, a, x3, st))) return rc;
   return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
                       pos_offset, dc);
@@ -1223,6 +1583,7 @@ struct FusedWs {
   float *bias_logq, *bias_lse;
   float *part_m, *part_l, *part_o_rows, *part_o_cols;
   int32_t* ids;  // hits mode only: [n_pad], both passes' stationary and streamed ids
+  float* thr;    // hard mode only: [n_pad], the rows' thresholds (-inf on padded rows)
 };
 struct FusedPlan {
   int D;
@@ -1238,7 +1599,7 @@ FusedPlan fused_plan(int64_t n, int dim) {
   p.per_split = round_up(ceil_div(p.n_pad, p.split), kTile);
   return p;
 }
-FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false, bool hits = false) {
+FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false, bool hits = false, bool hard = false) {
   FusedWs w;
   w.qb = cv.take<__bf16>(p.n_pad * p.D);
   w.cb = cv.take<__bf16>(p.n_pad * p.D);
@@ -1251,6 +1612,7 @@ FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false, bool hits =
   w.part_o_rows = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
   w.part_o_cols = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
   w.ids = hits ? cv.take<int32_t>(p.n_pad) : nullptr;  // last: the plain carve does not move
+  w.thr = hard ? cv.take<float>(p.n_pad) : nullptr;
   return w;
 }
 }  // namespace
@@ -1271,13 +1633,13 @@ namespace {
 int softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n, int32_t dim, const float* logq,
                  float* lse, float* row_loss, float* dq, float* dc, void* workspace, size_t workspace_bytes,
                  tt_stream_t stream, bool prepped, float loss_scale = 1.0f, float* loss = nullptr, bool x3 = false,
-                 const int32_t* ids = nullptr) {
+                 const int32_t* ids = nullptr, int64_t hard_k = 0, float* thr = nullptr) {
   int rc = check_common(q, ldq, n, c, ldc, n, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && row_loss && dq && dc, "tt_inbatch_softmax_xent: NULL output");
   const FusedPlan p = fused_plan(n, dim);
   Carver cv(workspace, workspace_bytes);
-  FusedWs w = carve_fused(cv, p, x3, ids != nullptr);
+  FusedWs w = carve_fused(cv, p, x3, ids != nullptr, hard_k > 0);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "tt_inbatch_softmax_xent: workspace %zu < required %zu", workspace_bytes,
                 cv.used());
@@ -1289,14 +1651,19 @@ int softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64
   jc.ids = ids, jc.ids_dst = w.ids;  // one padded copy serves rows and columns
   if (!prepped && (rc = prep(p.D, jq, jc, dim, p.n_pad, st))) return rc;
   const Plan pl{p.D, p.n_pad, p.n_pad, p.split, p.per_split};
+  if (hard_k > 0) {  // the rows' thresholds, from the rows pass's operands
+    const SelectArgs sel{w.qb, w.cb, w.bias_logq, n, p.n_pad, 0, w.qb_lo, w.cb_lo, w.ids, w.ids, clamp_k(hard_k),
+                         thr, w.thr};
+    if ((rc = launch_select(p.D, p.n_pad, sel, x3, st))) return rc;
+  }
   PassArgs ar{w.qb, w.cb, w.bias_logq, p.n_pad, p.n_pad, p.per_split, 0, w.part_m, w.part_l, w.part_o_rows,
-              w.qb_lo, w.cb_lo, w.ids, w.ids};
+              w.qb_lo, w.cb_lo, w.ids, w.ids, w.thr, nullptr};
   if ((rc = launch_pass_any<0>(pl, ar, x3, st))) return rc;
   if ((rc = combine_rows(p.D, st, w.part_m, w.part_l, w.part_o_rows, p.split, p.n_pad, q, ldq, c, ldc, logq, n, dim,
                          0, lse, row_loss, dq, w.bias_lse)))
     return rc;
   PassArgs ac{w.cb, w.qb, w.bias_lse, p.n_pad, p.n_pad, p.per_split, 0, nullptr, nullptr, w.part_o_cols,
-              w.cb_lo, w.qb_lo, w.ids, w.ids};
+              w.cb_lo, w.qb_lo, w.ids, w.ids, w.thr, w.bias_logq};
   if ((rc = launch_pass_any<1>(pl, ac, x3, st))) return rc;
   return combine_cols(p.D, st, w.part_o_cols, p.split, p.n_pad, q, ldq, c, ldc, lse, row_loss, logq, n, dim, 0, dc,
                       loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
@@ -1392,4 +1759,86 @@ extern "C" int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const f
   TT_REQUIRE(ids, "tt_inbatch_softmax_xent_hits: NULL ids");
   return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
                       loss_scale, loss, x3 != 0, ids);
+}
+
+// ---------------------------------------------------------------------------
+// Hard-negative mining (HARD): the K negatives with the largest S' of each
+// row kept, the others at weight 0 (include/tt.h, "hard negatives").
+// row_ids / col_ids (both or neither, may be NULL) as in the _hits entries.
+extern "C" size_t tt_inbatch_hard_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim, int32_t x3) {
+  return inbatch_ws_size(n_rows, n_cols, dim, x3 != 0, true, true);
+}
+
+extern "C" int tt_inbatch_hard_threshold(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
+                                         int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset,
+                                         const int32_t* row_ids, const int32_t* col_ids, int32_t x3, int64_t k,
+                                         float* thr, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  const char* fn = "tt_inbatch_hard_threshold";
+  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
+  if (rc) return rc;
+  TT_REQUIRE(thr, "%s: NULL thr", fn);
+  TT_REQUIRE(k >= 1, "%s: k must be >= 1", fn);
+  TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "%s: row_ids and col_ids go together", fn);
+  TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
+             "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
+  const Plan p = make_plan(n_rows, n_cols, dim);
+  Carver cv(workspace, workspace_bytes);
+  PassWs w = carve_pass(cv, p, x3 != 0, row_ids != nullptr, true);
+  if (!workspace || cv.used() > workspace_bytes)
+    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
+  hipStream_t st = to_stream(stream);
+  const PrepJob none{};
+  PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
+  jq.dst_lo = w.stat_lo;
+  jc.dst_lo = w.strm_lo;
+  jq.ids = row_ids, jq.ids_dst = w.stat_ids;
+  jc.ids = col_ids, jc.ids_dst = w.strm_ids;
+  if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
+  if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
+  const SelectArgs sel{w.stat, w.strm, w.bias, n_rows, p.strm_pad, pos_offset, w.stat_lo, w.strm_lo, w.stat_ids,
+                       w.strm_ids, clamp_k(k), thr, nullptr};
+  return launch_select(p.D, p.stat_pad, sel, x3 != 0, st);
+}
+
+extern "C" int tt_inbatch_xent_rows_hard(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
+                                         int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset,
+                                         const int32_t* row_ids, const int32_t* col_ids, int32_t x3,
+                                         const float* thr, float* lse, float* row_loss, float* dq, void* workspace,
+                                         size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "tt_inbatch_xent_rows_hard: row_ids and col_ids go together");
+  return xent_rows("tt_inbatch_xent_rows_hard", x3 != 0, row_ids, col_ids, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
+                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream, true, thr);
+}
+
+extern "C" int tt_inbatch_xent_cols_hard(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+                                         const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
+                                         int32_t dim, const float* logq, int64_t pos_offset, const int32_t* row_ids,
+                                         const int32_t* col_ids, int32_t x3, const float* thr, float* dc,
+                                         void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "tt_inbatch_xent_cols_hard: row_ids and col_ids go together");
+  return xent_cols("tt_inbatch_xent_cols_hard", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
+                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream, true, thr);
+}
+
+extern "C" size_t tt_inbatch_fused_hard_workspace_size(int64_t n, int32_t dim, int32_t x3) {
+  if (n < 1 || pick_dpad(dim) == 0) return 0;
+  Carver cv(nullptr, 0);
+  carve_fused(cv, fused_plan(n, dim), x3 != 0, true, true);
+  return cv.used();
+}
+
+extern "C" int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
+                                            int32_t dim, const float* logq, const int32_t* ids, int32_t x3,
+                                            int64_t k, float* lse, float* row_loss, float* dq, float* dc,
+                                            float* thr, float loss_scale, float* loss, void* workspace,
+                                            size_t workspace_bytes, tt_stream_t stream) {
+  using namespace tt;
+  clear_error();
+  TT_REQUIRE(k >= 1, "tt_inbatch_softmax_xent_hard: k must be >= 1");
+  TT_REQUIRE(thr, "tt_inbatch_softmax_xent_hard: NULL thr");
+  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
+                      loss_scale, loss, x3 != 0, ids, k, thr);
 }

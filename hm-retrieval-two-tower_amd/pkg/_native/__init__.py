@@ -381,6 +381,28 @@ _PROTOS = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
          c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "tt_inbatch_hard_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "tt_inbatch_hard_threshold": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_xent_rows_hard": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_xent_cols_hard": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_fused_hard_workspace_size": (c_size_t, [c_int64, c_int32, c_int32]),
+    "tt_inbatch_softmax_xent_hard": (
+        c_int32,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "tt_bruteforce_index_bytes": (c_size_t, [c_int64, c_int32]),
     "tt_bruteforce_build": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "tt_bruteforce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),

@@ -1100,7 +1100,8 @@ class ShardedTrainStep:
             if m.loss.reduction != "sum":
                 raise NotImplementedError("global negatives: the reference's SUM reduction only")
             loss = global_towers_inbatch_softmax_xent(qi, ci, m.query_tower.dense, m.candidate_tower.dense,
-                                                      self.comm, m.candidate_logq(x), m.candidate_ids(x))
+                                                      self.comm, m.candidate_logq(x), m.candidate_ids(x),
+                                                      num_hard_negatives=m.num_hard_negatives)
         else:
             loss = m.tower_loss(qi, ci, m.candidate_logq(x), m.candidate_ids(x))
         for t in m.towers:

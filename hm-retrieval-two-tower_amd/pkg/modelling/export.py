@@ -131,7 +131,8 @@ def save_two_tower(model, path_noext: str) -> None:
             "query_tower_units": model.query_tower.hidden_units,
             "candidate_tower_units": model.candidate_tower.hidden_units,
             "remove_accidental_hits": bool(model.remove_accidental_hits),
-            "normalize_embeddings": bool(model.normalize_embeddings), "temperature": model.temperature}
+            "normalize_embeddings": bool(model.normalize_embeddings), "temperature": model.temperature,
+            "num_hard_negatives": model.num_hard_negatives}
     arrays = _vocab_arrays(model.query_features, "query.")
     arrays.update(_vocab_arrays(model.candidate_features, "candidate."))
     arrays["logq.keys"] = np.asarray(list(lookup.keys()), dtype=str)
@@ -153,7 +154,8 @@ def load_two_tower(path_noext: str, device=None):
                           meta["candidate_tower_units"], candidate_prob_lookup=lookup, device=_device(device),
                           remove_accidental_hits=bool(meta.get("remove_accidental_hits", False)),
                           normalize_embeddings=bool(meta.get("normalize_embeddings", False)),
-                          temperature=meta.get("temperature"))
+                          temperature=meta.get("temperature"),
+                          num_hard_negatives=meta.get("num_hard_negatives"))
     model.query_tower.load_state_dict({k[len("query_tower."):]: v for k, v in tensors.items()
                                        if k.startswith("query_tower.")})
     model.candidate_tower.load_state_dict({k[len("candidate_tower."):]: v for k, v in tensors.items()

@@ -30,6 +30,7 @@ __all__ = [
     "dense_adagrad_many",
     "dense_adam",
     "inbatch_rows",
+    "inbatch_hard_threshold",
     "inbatch_cols",
     "inbatch_weight_rows",
     "inbatch_fused",
@@ -827,16 +828,29 @@ def _ids_pair(row_ids, col_ids, rows: torch.Tensor, cols: torch.Tensor):
     return _ids_ptr(row_ids, "row_ids", rows), _ids_ptr(col_ids, "col_ids", cols)
 
 
-def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], pos_offset: int = 0,
-                 want_dq: bool = True, x3: bool = False, row_ids: Optional[torch.Tensor] = None,
-                 col_ids: Optional[torch.Tensor] = None):
-    """Row pass: (lse [R], row_loss [R], dq [R,E] or None).  x3: fp32-faithful
-    products (tt_inbatch_xent_rows_x3, as inbatch_fused(x3=True)).
-    row_ids [R], col_ids [C] (int32, both or neither): accidental hits
-    removed (tt_inbatch_xent_rows_hits) — a column j other than row i's
-    positive with col_ids[j] == row_ids[i] is no negative of row i.  Ids are
-    compared for equality only, so all out-of-vocabulary rows (id 0) count
-    as one candidate."""
+def _hard_k(k) -> int:
+    """num_hard_negatives as the library takes it: a positive int."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"the number of hard negatives must be a positive int, got {k!r}")
+    return k
+
+
+def _hard_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool) -> torch.Tensor:
+    return Workspace.get(L.tt_inbatch_hard_workspace_size(R, C, E, int(x3)), device,
+                         "inbatch_hard_x3" if x3 else "inbatch_hard")
+
+
+def inbatch_hard_threshold(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], k: int,
+                           pos_offset: int = 0, x3: bool = False, row_ids: Optional[torch.Tensor] = None,
+                           col_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Hard-negative mining, the selection (tt_inbatch_hard_threshold): thr [R],
+    each row's threshold between its k-th and (k+1)-th largest negative score
+    S' = q_i . c_j - logq[j] in the arithmetic the passes use (x3, hits by
+    row_ids / col_ids as in inbatch_rows); -inf where the row has at most k
+    negatives.  Passed as thr= to inbatch_rows / inbatch_cols, only negatives
+    with S' >= thr keep their weight; negatives that tie the k-th value are
+    all kept (include/tt.h)."""
+    k = _hard_k(k)
     hits = _ids_pair(row_ids, col_ids, q, c)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
@@ -846,10 +860,48 @@ def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
     if c.shape[1] != E:
         raise ValueError("q and c must share the embedding size")
     L = lib()
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
+    ws = _hard_workspace(L, R, C, E, q.device, x3)
+    thr = torch.empty(R, dtype=torch.float32, device=q.device)
+    rid, cid = hits if hits is not None else (None, None)
+    check(L.tt_inbatch_hard_threshold(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
+                                      pos_offset, rid, cid, int(x3), k, thr.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream()))
+    return thr
+
+
+def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], pos_offset: int = 0,
+                 want_dq: bool = True, x3: bool = False, row_ids: Optional[torch.Tensor] = None,
+                 col_ids: Optional[torch.Tensor] = None, thr: Optional[torch.Tensor] = None):
+    """Row pass: (lse [R], row_loss [R], dq [R,E] or None).  x3: fp32-faithful
+    products (tt_inbatch_xent_rows_x3, as inbatch_fused(x3=True)).
+    row_ids [R], col_ids [C] (int32, both or neither): accidental hits
+    removed (tt_inbatch_xent_rows_hits) — a column j other than row i's
+    positive with col_ids[j] == row_ids[i] is no negative of row i.  Ids are
+    compared for equality only, so all out-of-vocabulary rows (id 0) count
+    as one candidate.  thr [R] (inbatch_hard_threshold's, same operands, ids
+    and x3): hard-negative mining (tt_inbatch_xent_rows_hard) — a negative
+    with S' below its row's threshold has weight 0."""
+    hits = _ids_pair(row_ids, col_ids, q, c)
+    _req(q, "q", torch.float32, 2)
+    _req(c, "c", torch.float32, 2)
+    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
+    R, E = q.shape
+    C = c.shape[0]
+    if c.shape[1] != E:
+        raise ValueError("q and c must share the embedding size")
+    L = lib()
     lse = torch.empty(R, dtype=torch.float32, device=q.device)
     row_loss = torch.empty(R, dtype=torch.float32, device=q.device)
     dq = torch.empty(R, E, dtype=torch.float32, device=q.device) if want_dq else None
+    if thr is not None:
+        rid, cid = hits if hits is not None else (None, None)
+        ws = _hard_workspace(L, R, C, E, q.device, x3)
+        check(L.tt_inbatch_xent_rows_hard(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
+                                          pos_offset, rid, cid, int(x3), _opt_ptr(thr, "thr", R), lse.data_ptr(),
+                                          row_loss.data_ptr(), dq.data_ptr() if dq is not None else None,
+                                          ws.data_ptr(), ws.numel(), _stream()))
+        return lse, row_loss, dq
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
     if hits is not None:
         rid, cid = hits
         check(L.tt_inbatch_xent_rows_hits(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
@@ -876,12 +928,15 @@ def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool
 
 def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
                  pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None, x3: bool = False,
-                 row_ids: Optional[torch.Tensor] = None, col_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 row_ids: Optional[torch.Tensor] = None, col_ids: Optional[torch.Tensor] = None,
+                 thr: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Column pass: dc [C,E] from every row's q [R,E], lse [R] and (optional,
     for the exact 1 - P_pos of confident rows) row_loss [R].  x3: fp32-faithful
     products (tt_inbatch_xent_cols_x3).  row_ids [R], col_ids [C] (int32, both
     or neither): accidental hits removed as in inbatch_rows, whose lse and
-    row_loss must come from the same ids (tt_inbatch_xent_cols_hits)."""
+    row_loss must come from the same ids (tt_inbatch_xent_cols_hits).
+    thr [R]: every row's hard-negative threshold, the one its lse came from
+    (tt_inbatch_xent_cols_hard)."""
     hits = _ids_pair(row_ids, col_ids, q, c)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
@@ -889,8 +944,17 @@ def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Opti
     R, E = q.shape
     C = c.shape[0]
     L = lib()
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
     dc = torch.empty(C, E, dtype=torch.float32, device=q.device)
+    if thr is not None:
+        rid, cid = hits if hits is not None else (None, None)
+        ws = _hard_workspace(L, R, C, E, q.device, x3)
+        check(L.tt_inbatch_xent_cols_hard(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
+                                          _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
+                                          _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3),
+                                          _opt_ptr(thr, "thr", R), dc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream()))
+        return dc
+    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
     if hits is not None:
         rid, cid = hits
         check(L.tt_inbatch_xent_cols_hits(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
@@ -952,7 +1016,7 @@ def inbatch_prep(x: torch.Tensor, operand: int, logq: Optional[torch.Tensor], ws
 
 def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], ws: Optional[torch.Tensor] = None,
                   prepped: bool = False, loss_scale: Optional[float] = None, x3: bool = False,
-                  ids: Optional[torch.Tensor] = None):
+                  ids: Optional[torch.Tensor] = None, hard_k: Optional[int] = None):
     """Single-device loss + gradients (both passes, shared bf16 prep):
     (lse [B], row_loss [B], dq [B,E], dc [B,E]).  prepped: both operands were
     already prepared into `ws` by inbatch_prep (ordered before this call).
@@ -963,7 +1027,17 @@ def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor]
     ids [B] (int32): accidental hits removed (tt_inbatch_softmax_xent_hits) —
     a column j != i with ids[j] == ids[i] is no negative of row i; equality
     only, so all out-of-vocabulary rows (id 0) count as one candidate.  This
-    departs from the reference's loss; not with prepped."""
+    departs from the reference's loss; not with prepped.
+    hard_k: hard-negative mining (tt_inbatch_softmax_xent_hard: one
+    preparation, then selection, rows, cols) — only each row's hard_k
+    largest-scoring negatives (and those tying the last) keep their weight;
+    with or without ids, either arithmetic, not with prepped.  The row
+    thresholds come back as one more value after dc: (lse, row_loss, dq, dc,
+    thr[, loss])."""
+    if hard_k is not None:
+        hard_k = _hard_k(hard_k)
+        if prepped:
+            raise ValueError("hard_k: the hard-negative entry prepares its operands itself (prepped=False)")
     if ids is not None:
         if prepped:
             raise ValueError("ids: the accidental-hit entry prepares its operands itself (prepped=False)")
@@ -977,6 +1051,22 @@ def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor]
     if prepped and ws is None:
         raise ValueError("prepped=True needs the workspace the operands were prepared into")
     L = lib()
+    if hard_k is not None:
+        ws = Workspace.get(L.tt_inbatch_fused_hard_workspace_size(B, E, int(x3)), q.device,
+                           "inbatch_fused_hard_x3" if x3 else "inbatch_fused_hard")
+        lse = torch.empty(B, dtype=torch.float32, device=q.device)
+        row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
+        dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
+        dc = torch.empty(B, E, dtype=torch.float32, device=q.device)
+        thr = torch.empty(B, dtype=torch.float32, device=q.device)
+        loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
+        check(L.tt_inbatch_softmax_xent_hard(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
+                                             idp if ids is not None else None, int(x3), hard_k, lse.data_ptr(),
+                                             row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(), thr.data_ptr(),
+                                             float(loss_scale if loss_scale is not None else 1.0),
+                                             loss.data_ptr() if loss is not None else None, ws.data_ptr(),
+                                             ws.numel(), _stream()))
+        return (lse, row_loss, dq, dc, thr, loss) if loss is not None else (lse, row_loss, dq, dc, thr)
     if ids is not None:
         ws = Workspace.get(L.tt_inbatch_fused_hits_workspace_size(B, E, int(x3)), q.device,
                            "inbatch_fused_hits_x3" if x3 else "inbatch_fused_hits")

@@ -61,22 +61,52 @@ def x3_scores() -> bool:
 # [0, 1] turns the loss NaN.  weights=None issues the calls it always issued.
 
 
-def weighted_inbatch_grads(q, c, logq, weights, ids=None, x3: Optional[bool] = None):
+# num_hard_negatives (every loss below, optional): hard-negative mining, a
+# positive int K (TensorFlow Recommenders' Retrieval(num_hard_negatives=K)).
+# Of each row's negatives only the K with the largest logits S' = q_i . c_j -
+# logq[j] keep their weight in the loss and in both gradients; it applies
+# after temperature / cosine scoring, logQ and accidental hits, as in TFRS.
+# A selection kernel finds each row's threshold thr[i], the midpoint of its
+# K-th and (K+1)-th largest negative score, and the HARD form of the pass
+# kernels drops every negative below it (include/tt.h, tt_inbatch_*_hard).
+# Negatives that tie the K-th value are all kept — the one departure from
+# tf.math.top_k's index tie-break.  K at or above the number of negatives is
+# the loss without mining, bit for bit.  None issues the calls it always
+# issued.
+
+
+def _check_hard(k):
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+        raise ValueError(f"num_hard_negatives must be a positive int or None, got {k!r}")
+    return k
+
+
+def weighted_inbatch_grads(q, c, logq, weights, ids=None, x3: Optional[bool] = None,
+                           num_hard_negatives: Optional[int] = None):
     """(wloss [B], dq, dc) of the weighted single-device loss: rows, fold,
-    cols, with the operands and ids the unweighted entries take."""
+    cols, with the operands and ids the unweighted entries take;
+    num_hard_negatives: select, rows, fold, cols."""
     x3 = x3_scores() if x3 is None else x3
-    lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids)
+    if _check_hard(num_hard_negatives) is None:
+        lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids)
+        lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
+        dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids)
+        return wloss, dq, dc
+    thr = hip_ops.inbatch_hard_threshold(q, c, logq, num_hard_negatives, x3=x3, row_ids=ids, col_ids=ids)
+    lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids, thr=thr)
     lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
-    dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids)
+    dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids, thr=thr)
     return wloss, dq, dc
 
 
 class _InBatchXent(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, c, logq, scale, ids=None, weights=None, weight_scale=1.0):
+    def forward(ctx, q, c, logq, scale, ids=None, weights=None, weight_scale=1.0, hard=None):
         if weights is not None:
             scale = scale * weight_scale
-            row_loss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids)
+            row_loss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
+        elif hard is not None:
+            _, row_loss, dq, dc, _ = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids, hard_k=hard)
         else:
             lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids)
         ctx.scale = scale
@@ -87,7 +117,7 @@ class _InBatchXent(torch.autograd.Function):
     def backward(ctx, g):
         dq, dc = ctx.saved_tensors
         s = g * ctx.scale
-        return dq * s, dc * s, None, None, None, None, None
+        return dq * s, dc * s, None, None, None, None, None, None
 
 
 _SIDE: dict = {}
@@ -219,20 +249,20 @@ class _TowersInBatchXent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None,
-                weights=None, weight_scale=1.0):
+                weights=None, weight_scale=1.0, hard=None):
         ctx.pair = _paired(qi, stack_q, stack_c)
         ctx.on_dx = on_dx
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
             return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower,
-                                              ids=ids, weights=weights, weight_scale=weight_scale)
+                                              ids=ids, weights=weights, weight_scale=weight_scale, hard=hard)
         main = torch.cuda.current_stream()
         side = _tower_stream(qi.device)
         # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
         # stream right after its MLP (the workspace is fetched before the fork)
         # (not under x3_scores() or with ids: those entries prepare their operands themselves;
         # not with normalised outputs: it would prepare the un-normalised ones)
-        split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None
+        split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None and hard is None
                       and not (stack_q.normalize or stack_c.normalize))
         ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
@@ -245,11 +275,11 @@ class _TowersInBatchXent(torch.autograd.Function):
             hip_ops.inbatch_prep(qa[-1], 0, None, ws)
         main.wait_stream(side)
         return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws,
-                                          ids, weights, weight_scale)
+                                          ids, weights, weight_scale, hard)
 
     @staticmethod
     def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None, ids=None,
-                weights=None, weight_scale=1.0):
+                weights=None, weight_scale=1.0, hard=None):
         if weights is not None:
             scale = scale * weight_scale  # w_max: the loss is linear in w
         ctx.stacks = (stack_q, stack_c)
@@ -261,8 +291,11 @@ class _TowersInBatchXent(torch.autograd.Function):
         # the un-normalised ones right after it (one launch, in place)
         q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])
         if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
-            wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids)
+            wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
             loss = hip_ops.loss_sum(wloss, scale)
+        elif hard is not None:  # hard negatives (its own preparation and workspace), either arithmetic, ids or none
+            _, _, dq, dc, _, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids,
+                                                          hard_k=hard)
         elif ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
             _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids)
         elif x3_scores():  # fp32-faithful scores (its own preparation and workspace)
@@ -283,7 +316,7 @@ class _TowersInBatchXent(torch.autograd.Function):
         stack_q, stack_c = ctx.stacks
         if ctx.pair:  # (on_dx unused: on_tower then applies each tower's whole update)
             return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, ctx.on_tower),
-                    None, None, None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None, None, None)
         on_dx = ctx.on_dx
         main = torch.cuda.current_stream()
         side = _tower_stream(dq.device)
@@ -300,12 +333,13 @@ class _TowersInBatchXent(torch.autograd.Function):
         if ctx.on_tower is not None:
             ctx.on_tower(0, gqi, gflat_q)
         main.wait_stream(side)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None, None
 
 
 def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], comm,
                          rows=None, cols=None, x3: Optional[bool] = None, ids: Optional[torch.Tensor] = None,
-                         weights: Optional[torch.Tensor] = None, fold=None):
+                         weights: Optional[torch.Tensor] = None, fold=None,
+                         num_hard_negatives: Optional[int] = None, threshold=None):
     """This rank's share of the in-batch loss over the GLOBAL batch
     (two_tower_model.py:113-122 with the batch split over the ranks: row i's
     negatives are every candidate of every rank).  q, c: this rank's [b, E]
@@ -328,15 +362,28 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     dq scaled in place; hip_ops.inbatch_weight_rows unless injected), the
     all-gather of [lse, row_loss] then carries the folded values and nothing
     else moves; the first value returned is then wloss, the weighted terms.
-    The one-rank shortcut through the single-device entry is not taken."""
+    The one-rank shortcut through the single-device entry is not taken.
+    num_hard_negatives: hard-negative mining over the global batch — the
+    selection runs on this rank's rows against the gathered columns
+    (threshold(q, C, L, k, pos_offset=off[, row_ids, col_ids]) -> thr [b];
+    hip_ops.inbatch_hard_threshold unless injected), the rows pass takes thr=
+    as a keyword, thr joins the all-gather of [lse, row_loss] as a third
+    column, and the cols pass takes every row's thr= (injected rows / cols
+    receive it as a keyword)."""
     if x3 is None:
         x3 = x3_scores()
+    hard = _check_hard(num_hard_negatives)
     if (WORLD1_FUSED and weights is None and comm.world == 1 and rows is None and cols is None
-            and not getattr(comm, "always", False)):
+            and threshold is None and not getattr(comm, "always", False)):
         # one rank: its rows are every row and its columns every column — the
         # single-device entry (one shared preparation of q and c for both passes)
+        if hard is not None:
+            _, row_loss, dq, dc, _ = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids, hard_k=hard)
+            return row_loss, dq, dc
         _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids)
         return row_loss, dq, dc
+    if hard is not None and threshold is None:
+        threshold = functools.partial(hip_ops.inbatch_hard_threshold, x3=x3)
     rows = rows or (functools.partial(hip_ops.inbatch_rows, x3=True) if x3 else hip_ops.inbatch_rows)
     cols = cols or (functools.partial(hip_ops.inbatch_cols, x3=True) if x3 else hip_ops.inbatch_cols)
     b = q.shape[0]
@@ -347,12 +394,23 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
         I = comm.all_gather(ids)                               # [G b]: every candidate's id
         rows = functools.partial(rows, row_ids=ids, col_ids=I)
         cols = functools.partial(cols, row_ids=I, col_ids=ids)
+        if hard is not None:
+            threshold = functools.partial(threshold, row_ids=ids, col_ids=I)
+    if hard is not None:
+        thr = threshold(q, C, L, hard, pos_offset=off)         # [b]: this rank's rows against every column
+        rows = functools.partial(rows, thr=thr)
     lse, row_loss, dq = rows(q, C, L, pos_offset=off)
     if weights is not None:
         lse, row_loss_w, wloss = (fold or hip_ops.inbatch_weight_rows)(weights, lse, row_loss, dq)
     Qa = comm.all_gather(q)                                    # [G b, E]
     if comm.world == 1 and not getattr(comm, "always", False):
         lse_a, loss_a = lse, (row_loss if weights is None else row_loss_w)  # one rank: its rows are every row (no stack / split copies)
+        if hard is not None:
+            cols = functools.partial(cols, thr=thr)
+    elif hard is not None:
+        st = comm.all_gather(torch.stack([lse, row_loss if weights is None else row_loss_w, thr.to(lse.dtype)], 1))  # [G b, 3]: and every row's thr
+        lse_a, loss_a = st[:, 0].contiguous(), st[:, 1].contiguous()
+        cols = functools.partial(cols, thr=st[:, 2].contiguous())
     else:
         st = comm.all_gather(torch.stack([lse, row_loss if weights is None else row_loss_w], 1))  # [G b, 2]: every row's lse and loss
         lse_a, loss_a = st[:, 0].contiguous(), st[:, 1].contiguous()
@@ -367,7 +425,7 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm, ids=None, weights=None,
-                weight_scale=1.0):
+                weight_scale=1.0, hard=None):
         if weights is not None:
             scale = scale * weight_scale
         ctx.pair = _paired(qi, stack_q, stack_c)
@@ -380,7 +438,7 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
             qa = stack_q.forward_acts(qi, flat_q)
             _tower_join(qi)
         q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])  # cosine scoring (as _TowersInBatchXent)
-        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids, weights=weights)
+        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids, weights=weights, num_hard_negatives=hard)
         unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
         ctx.stacks = (stack_q, stack_c)
         ctx.nq = len(qa)
@@ -396,63 +454,76 @@ class _GlobalTowersInBatchXent(torch.autograd.Function):
         stack_q, stack_c = ctx.stacks
         if ctx.pair:
             return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None, None,
-                    None, None)
+                    None, None, None)
         with _TowerFork(dq):
             gci, gflat_c = stack_c.backward_acts(ca, flat_c, dc, s, ctx.needs_input_grad[1])
         gqi, gflat_q = stack_q.backward_acts(qa, flat_q, dq, s, ctx.needs_input_grad[0])
         _tower_join(dq)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None
+        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None
 
 
 def global_towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c, comm,
                                        logq: Optional[torch.Tensor] = None,
                                        ids: Optional[torch.Tensor] = None,
                                        weights: Optional[torch.Tensor] = None,
-                                       weight_scale: float = 1.0) -> torch.Tensor:
+                                       weight_scale: float = 1.0,
+                                       num_hard_negatives: Optional[int] = None) -> torch.Tensor:
     """towers_inbatch_softmax_xent with the negatives of every rank (SUM
     reduction, the reference's runner.py:78-83).  ids: this rank's candidate
     ids (accidental hits removed over the global batch).  weights: this
-    rank's normalised sample weights, weight_scale the global w_max."""
+    rank's normalised sample weights, weight_scale the global w_max.
+    num_hard_negatives: hard negatives mined over the global batch."""
     return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm, ids,
-                                          weights, float(weight_scale))
+                                          weights, float(weight_scale), _check_hard(num_hard_negatives))
 
 
 def towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c,
                                 logq: Optional[torch.Tensor] = None, reduction: str = "sum",
                                 on_tower=None, on_dx=None, ids: Optional[torch.Tensor] = None,
-                                weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0) -> torch.Tensor:
+                                weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0,
+                                num_hard_negatives: Optional[int] = None) -> torch.Tensor:
     """Loss of the query tower on qi against the candidate tower on ci (tower
     inputs [B, *]), fused into one autograd node; stack_* are DenseStacks.
     on_tower(i, input_grad, flat_grad), if given, is called in the backward as
     soon as tower i's (0 query, 1 candidate) gradients exist, on the stream and
     workspace scope they were produced in (the fused train step applies the
     optimizer there).  ids [B] (int32): accidental hits removed.  weights [B]
-    (fp32, in [0, 1]) and weight_scale: sample weights (see above)."""
+    (fp32, in [0, 1]) and weight_scale: sample weights (see above).
+    num_hard_negatives: hard-negative mining (see above)."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / qi.shape[0]
     return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, on_tower,
-                                    on_dx, ids, weights, float(weight_scale))
+                                    on_dx, ids, weights, float(weight_scale), _check_hard(num_hard_negatives))
 
 
 def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor] = None,
                          reduction: str = "sum", ids: Optional[torch.Tensor] = None,
-                         weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0) -> torch.Tensor:
+                         weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0,
+                         num_hard_negatives: Optional[int] = None) -> torch.Tensor:
     """Loss of query rows q [B,E] against candidates c [B,E] (positive of row
     i is column i), logq [B] the per-candidate log sampling probability.
     ids [B] (int32): accidental hits removed (see above).  weights [B] (fp32,
-    in [0, 1]) and weight_scale: sample weights (see above)."""
+    in [0, 1]) and weight_scale: sample weights (see above).
+    num_hard_negatives: hard-negative mining (see above)."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
     scale = 1.0 if reduction == "sum" else 1.0 / q.shape[0]
+    hard = _check_hard(num_hard_negatives)
     if not q.requires_grad and not c.requires_grad:
         # the scores the training loss is computed from, in either mode
-        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids, col_ids=ids)
+        if hard is not None:
+            thr = hip_ops.inbatch_hard_threshold(q, c, logq, hard, x3=x3_scores(), row_ids=ids, col_ids=ids)
+            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids,
+                                                    col_ids=ids, thr=thr)
+        else:
+            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids,
+                                                    col_ids=ids)
         if weights is not None:
             _, _, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss)
             return hip_ops.loss_sum(wloss, scale * weight_scale)
         return hip_ops.loss_sum(row_loss, scale)
-    return _InBatchXent.apply(q, c, logq, scale, ids, weights, float(weight_scale))
+    return _InBatchXent.apply(q, c, logq, scale, ids, weights, float(weight_scale), hard)
 
 
 class InBatchSoftmaxCrossEntropy:
@@ -464,8 +535,8 @@ class InBatchSoftmaxCrossEntropy:
             raise ValueError("the in-batch loss is defined on logits (from_logits=True)")
         self.reduction = str(reduction).lower().split(".")[-1]
 
-    def __call__(self, q, c, logq=None, ids=None, weights=None, weight_scale: float = 1.0):
-        return inbatch_softmax_xent(q, c, logq, self.reduction, ids, weights, weight_scale)
+    def __call__(self, q, c, logq=None, ids=None, weights=None, weight_scale: float = 1.0, num_hard_negatives=None):
+        return inbatch_softmax_xent(q, c, logq, self.reduction, ids, weights, weight_scale, num_hard_negatives)
 
 
 # Name the reference compiles with.

@@ -106,6 +106,15 @@ class TwoTowerModel(AbstractKerasModel):
         training logits cos / T (before logQ), an index built from the
         candidate tower and queried through the query tower returns cos / T,
         and the ranking does not depend on T.  None: T = 1.
+    num_hard_negatives: Optional[int]
+        None (the default): every negative of the batch enters the loss.  A
+        positive int K: hard-negative mining (TensorFlow Recommenders'
+        Retrieval(num_hard_negatives=K)) — of each row's negatives only the K
+        with the largest logits (after temperature, logQ and accidental
+        hits) keep their weight, in training and in evaluation, on every
+        step path; negatives that tie the K-th logit are all kept.  K at or
+        above the batch size is the default loss bit for bit.  Anything but
+        a positive int raises ValueError.
     """
 
     def __init__(self, query_features: List[Feature], candidate_features: List[Feature], candidate_id_col: str,
@@ -114,7 +123,13 @@ class TwoTowerModel(AbstractKerasModel):
                  candidate_prob_lookup: Optional[Dict[str, float]] = None,
                  device: Optional[torch.device] = None, seed: Optional[int] = None,
                  fused_optimizer_apply: bool = False, remove_accidental_hits: bool = False,
-                 normalize_embeddings: bool = False, temperature: Optional[float] = None):
+                 normalize_embeddings: bool = False, temperature: Optional[float] = None,
+                 num_hard_negatives: Optional[int] = None):
+        if num_hard_negatives is not None and (isinstance(num_hard_negatives, bool)
+                                               or not isinstance(num_hard_negatives, (int, np.integer))
+                                               or num_hard_negatives < 1):
+            raise ValueError(f"num_hard_negatives={num_hard_negatives!r} must be a positive int or None")
+        self.num_hard_negatives = None if num_hard_negatives is None else int(num_hard_negatives)
         self.normalize_embeddings = bool(normalize_embeddings)
         if temperature is not None:
             temperature = float(temperature)
@@ -267,6 +282,8 @@ class TwoTowerModel(AbstractKerasModel):
         ids: candidate_ids(x) (accidental hits removed), or None.  weights:
         sample_weights(x), or None (an unweighted batch: the calls as ever)."""
         wkw = {} if weights is None else {"weights": weights, "weight_scale": float(self.sample_weight_scale)}
+        if self.num_hard_negatives is not None:  # hard-negative mining, on every path through here
+            wkw["num_hard_negatives"] = self.num_hard_negatives
         if torch.is_grad_enabled():
             return towers_inbatch_softmax_xent(qi, ci, self.query_tower.dense, self.candidate_tower.dense, logq,
                                                self.loss.reduction, getattr(self, "_on_tower", None),

@@ -539,6 +539,92 @@ int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const float* c,
                                  float* loss, void* workspace,
                                  size_t workspace_bytes, tt_stream_t stream);
 
+/* Opt-in hard-negative mining (TensorFlow Recommenders' Retrieval task,
+ * num_hard_negatives = K): of each row's negatives only the K with the
+ * largest logits enter the cross-entropy.  The reference has no such option;
+ * the entries above do not change.  Order as in TFRS: temperature (applied
+ * before the loss), logQ, accidental hits, then hard negatives.
+ *
+ * S'[i][j] = q_i . c_j - logq[j] is the score the pass kernels form, in
+ * either arithmetic (bf16 operands, or the bf16x3 products for x3 != 0), and
+ * -inf on an accidental hit when ids are given.  For k >= 1 and each row i,
+ * over the row's negatives j != pos(i) (hits included, as -inf):
+ *
+ *   a >= b      the k-th and (k+1)-th largest S'[i][j]
+ *   thr[i]      = fl32(0.5 a + 0.5 b); if that rounds to b while a > b: a
+ *   thr[i]      = -inf if the row has <= k negatives, or b = -inf
+ *   (i, j) kept iff S'[i][j] >= thr[i]
+ *
+ * TIES: every negative that ties the k-th value is kept, so a row may keep
+ * more than k.  This is the one departure from tf.math.top_k, which breaks
+ * ties by index and keeps exactly k.
+ *
+ * A dropped pair has weight 0 in lse_i, dq_i and dc_j, exactly like a masked
+ * accidental hit (its score becomes -inf after the score MFMAs).  The
+ * positive is always kept and enters in fp32 exactly as in the plain entries.
+ *
+ * Why the midpoint: under x3 the rows pass streams c and the cols pass
+ * streams q, so the two cross products hi.lo / lo.hi are added in different
+ * orders and one S'[i][j] can differ in its last bits between the passes.  A
+ * threshold inside the gap (a, b) gives both passes the same kept set
+ * whenever that difference is below half the gap.  With bf16 operands the
+ * products are exact and both passes add them in the same k order: the bits
+ * agree.
+ *
+ * tt_inbatch_hard_threshold computes thr [n_rows] from the rows pass's own
+ * MFMA sequence (same operand roles, k order and accumulator start), so its
+ * S' is the rows pass's bit for bit.  It is exact and deterministic (an
+ * 8-bit-digit radix select on the order-preserving integer key of S', integer
+ * histograms only), puts no cap on k, and synchronises with nothing: it
+ * captures into a graph.  k < 1 is TT_ERR_BAD_ARG.
+ *
+ * Invariants: with k >= the number of negatives, or thr all -inf, every
+ * output of the _hard entries equals the corresponding plain, x3 or hits
+ * entry's bit for bit.  Sample weights (tt_inbatch_weight_rows) compose as
+ * before: select, rows, fold, cols.
+ *
+ * Arguments, checks, error codes and the x3 flag as the _hits entries';
+ * row_ids / col_ids (ids for the fused form) may both be NULL: no hits are
+ * removed.  The rows form takes thr [n_rows]; the cols form takes thr of all
+ * n_rows rows, as it takes lse.  The fused form (single device: one
+ * preparation, then select, rows, cols) returns thr [n] to the caller and
+ * writes the in-launch *loss (loss may be NULL).  The workspaces are the
+ * _hits ones plus a padded threshold vector. */
+size_t tt_inbatch_hard_workspace_size(int64_t n_rows, int64_t n_cols,
+                                      int32_t dim, int32_t x3);
+int tt_inbatch_hard_threshold(const float* q, int64_t ldq, int64_t n_rows,
+                              const float* c, int64_t ldc, int64_t n_cols,
+                              int32_t dim, const float* logq,
+                              int64_t pos_offset, const int32_t* row_ids,
+                              const int32_t* col_ids, int32_t x3, int64_t k,
+                              float* thr, void* workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+int tt_inbatch_xent_rows_hard(const float* q, int64_t ldq, int64_t n_rows,
+                              const float* c, int64_t ldc, int64_t n_cols,
+                              int32_t dim, const float* logq,
+                              int64_t pos_offset, const int32_t* row_ids,
+                              const int32_t* col_ids, int32_t x3,
+                              const float* thr, float* lse, float* row_loss,
+                              float* dq, void* workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+int tt_inbatch_xent_cols_hard(const float* q, int64_t ldq, int64_t n_rows,
+                              const float* lse, const float* row_loss,
+                              const float* c, int64_t ldc, int64_t n_cols,
+                              int32_t dim, const float* logq,
+                              int64_t pos_offset, const int32_t* row_ids,
+                              const int32_t* col_ids, int32_t x3,
+                              const float* thr, float* dc, void* workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+size_t tt_inbatch_fused_hard_workspace_size(int64_t n, int32_t dim, int32_t x3);
+int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const float* c,
+                                 int64_t ldc, int64_t n, int32_t dim,
+                                 const float* logq, const int32_t* ids,
+                                 int32_t x3, int64_t k, float* lse,
+                                 float* row_loss, float* dq, float* dc,
+                                 float* thr, float loss_scale, float* loss,
+                                 void* workspace, size_t workspace_bytes,
+                                 tt_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * K11+K12  Brute-force scoring with fused top-K.
  * Replaces BruteForceIndex.call (pkg/modelling/indices/brute_force.py:76-81):
