@@ -1123,7 +1123,20 @@ __device__ __forceinline__ void loss_sum_block(const LossSum& L) {
   if (threadIdx.x == 0) L.out[0] = red[0] * L.scale;
 }
 
-template <int D>
+//
+// MIXED (opt-in, tt_inbatch_xent_cols_mixed / tt_inbatch_softmax_xent_mixed):
+// a column need not have a positive row.  Column j's positive is row
+// j + pos_offset when that lies in [0, n_rows); a column without one (a
+// sampled extra negative) is dc_j = exp(-logq_j) * sum_s O_s[j] alone, and
+// nothing of q / lse / row_loss is read for it (1 - P_pos and q_pos enter the
+// one final expression as zeros, so a column with a positive is the default
+// form's bit for bit).  n_rows is loss.n, which this form's launches fill with
+// or without a loss block.  The pass kernel needs no form of its own: its
+// mask_diag only ever turns a score into -inf, and such a column's would-be
+// positive row j + pos_offset >= n_rows is either a padded streamed row,
+// whose bias is -inf already (weight 0 with or without the mask), or past the
+// streamed extent, where no tile holds it.
+template <int D, bool MIXED = false>
 __global__ void __launch_bounds__(256) combine_cols_kernel(const float* __restrict__ part_o, int nsplit,
                                                            int64_t n_stat_pad, const float* __restrict__ q,
                                                            int64_t ldq, const float* __restrict__ c, int64_t ldc,
@@ -1143,11 +1156,18 @@ __global__ void __launch_bounds__(256) combine_cols_kernel(const float* __restri
   const float lq = logq ? logq[j] : 0.0f;
   const float scale = logq ? expf(-lq) : 1.0f;
   const int64_t pos = j + pos_offset;
+  bool has_pos = true;  // uniform over the row's LPR lanes
+  if constexpr (MIXED) has_pos = pos >= 0 && pos < loss.n;
   float qe[4];  // q_pos, loaded with the first partials (clamped past dim, dropped)
 #pragma unroll
-  for (int u = 0; u < 4; ++u) qe[u] = q[pos * ldq + min(4 * sub + u, dim - 1)];
+  for (int u = 0; u < 4; ++u) {
+    if constexpr (MIXED) qe[u] = has_pos ? q[pos * ldq + min(4 * sub + u, dim - 1)] : 0.0f;
+    else qe[u] = q[pos * ldq + min(4 * sub + u, dim - 1)];
+  }
   float omp;  // 1 - P_pos
-  if (row_loss) {
+  if (MIXED && !has_pos) {
+    omp = 0.0f;
+  } else if (row_loss) {
     omp = -expm1f(-row_loss[pos]);
   } else {
     float dot = 0.0f;
@@ -1177,6 +1197,7 @@ __global__ void __launch_bounds__(256) combine_cols_kernel(const float* __restri
     if (e < dim) dc[j * dim + e] = o[u] * scale - omp * qe[u];
   }
 }
+
 
 int pick_dpad(int dim) {
   if (dim <= 32) return 32;
@@ -1324,6 +1345,27 @@ int combine_cols(int D, hipStream_t st, const float* po, int nsplit, int64_t n_s
   return TT_OK;
 }
 
+// The MIXED form: columns whose positive row j + pos_offset falls outside
+// [0, n_rows) have none.
+int combine_cols_mixed(int D, hipStream_t st, const float* po, int nsplit, int64_t n_stat_pad, const float* q,
+                       int64_t ldq, const float* c, int64_t ldc, const float* lse, const float* row_loss,
+                       const float* logq, int64_t n, int dim, int64_t pos_offset, float* dc, int64_t n_rows,
+                       const LossSum& loss_in = LossSum{}) {
+  const dim3 grid(static_cast<unsigned>(ceil_div(n, 1024 / D) + (loss_in.x ? 1 : 0)));
+  LossSum loss = loss_in;
+  loss.n = n_rows;  // the MIXED form's n_rows (a loss block sums row_loss [n_rows])
+  switch (D) {
+    case 32: hipLaunchKernelGGL((combine_cols_kernel<32, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
+                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
+    case 64: hipLaunchKernelGGL((combine_cols_kernel<64, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
+                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
+    default: hipLaunchKernelGGL((combine_cols_kernel<128, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
+                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
+  }
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
 template <int D, int MODE, bool X3, bool HITS, bool HARD>
 int launch_pass_d(dim3 grid, const PassArgs& a, hipStream_t st) {
   // HITS: the streamed ids' ring slot and the workgroup's stationary ids;
@@ -1463,13 +1505,15 @@ int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* co
 int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
               int64_t n_rows, const float* lse, const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
               int32_t dim, const float* logq, int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes,
-              tt_stream_t stream, bool hard = false, const float* thr = nullptr) {
+              tt_stream_t stream, bool hard = false, const float* thr = nullptr, bool mixed = false) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && dc, "%s: NULL lse/dc", fn);
   TT_REQUIRE(!hard || thr, "%s: NULL thr", fn);
-  TT_REQUIRE(pos_offset >= 0 && n_cols + pos_offset <= n_rows,
+  // mixed: a column whose positive falls outside [0, n_rows) has none
+  TT_REQUIRE(mixed || (pos_offset >= 0 && n_cols + pos_offset <= n_rows),
              "%s: positives [pos_offset, pos_offset+n_cols) exceed n_rows", fn);
+  TT_REQUIRE(pos_offset > -(1ll << 30) && pos_offset < (1ll << 30), "%s: pos_offset out of range", fn);
   const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
   Carver cv(workspace, workspace_bytes);
   PassWs w = carve_pass(cv, p, x3, row_ids != nullptr, hard);
@@ -1489,6 +1533,9 @@ int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* co
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o,
              w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids, w.thr, w.stat_bias};
   if ((rc = launch_pass_any<1>(p, a, x3, st))) return rc;
+  if (mixed)
+    return combine_cols_mixed(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols,
+                              dim, pos_offset, dc, n_rows);
   return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
                       pos_offset, dc);
 }
@@ -1841,4 +1888,137 @@ extern "C" int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const f
   TT_REQUIRE(thr, "tt_inbatch_softmax_xent_hard: NULL thr");
   return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
                       loss_scale, loss, x3 != 0, ids, k, thr);
+}
+
+// ---------------------------------------------------------------------------
+// Mixed negative sampling (MIXED): the batch's columns followed by extra
+// columns that are negatives of every row (include/tt.h, "mixed negatives").
+// The rows pass and the selection take n_cols > n_rows as they are; the cols
+// entry below lifts the rule that every column has a positive row.
+extern "C" size_t tt_inbatch_mixed_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim, int32_t x3) {
+  return inbatch_ws_size(n_rows, n_cols, dim, x3 != 0, true, true);
+}
+
+extern "C" int tt_inbatch_xent_cols_mixed(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+                                          const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
+                                          int32_t dim, const float* logq, int64_t pos_offset, const int32_t* row_ids,
+                                          const int32_t* col_ids, int32_t x3, const float* thr, float* dc,
+                                          void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr),
+             "tt_inbatch_xent_cols_mixed: row_ids and col_ids go together");
+  return xent_cols("tt_inbatch_xent_cols_mixed", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
+                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream, thr != nullptr, thr, true);
+}
+
+// Single device: q [n] against c [n + m].  One bf16 preparation of each
+// operand, padded to 128 rows, serves both passes: the rows pass streams c's
+// image over round_up(n + m, 64) rows and the cols pass q's over
+// round_up(n, 64), the extents (and so the split geometry and every sum's
+// order) of the rectangular entries called at n_cols = n + m.  m = 0 is the
+// square fused entry itself.
+namespace tt {
+namespace {
+struct MixedWs {
+  __bf16 *qb, *cb;
+  __bf16 *qb_lo, *cb_lo;
+  float *bias_logq, *bias_lse;
+  float *part_m, *part_l, *part_o_rows, *part_o_cols;
+  int32_t* ids;
+  float* thr;
+};
+struct MixedPlan {
+  Plan rows, cols;        // rows: stationary q, streamed c; cols: the other way round
+  int64_t q_pad, c_pad;   // rows of the two images (multiples of 128)
+};
+MixedPlan mixed_plan(int64_t n, int64_t m, int dim) {
+  MixedPlan p;
+  p.rows = make_plan(n, n + m, dim);
+  p.cols = make_plan(n + m, n, dim);
+  p.q_pad = p.rows.stat_pad;  // >= cols.strm_pad
+  p.c_pad = p.cols.stat_pad;  // >= rows.strm_pad
+  return p;
+}
+MixedWs carve_mixed(Carver& cv, const MixedPlan& p, bool x3, bool hits, bool hard) {
+  const int D = p.rows.D;
+  MixedWs w;
+  w.qb = cv.take<__bf16>(p.q_pad * D);
+  w.cb = cv.take<__bf16>(p.c_pad * D);
+  w.qb_lo = x3 ? cv.take<__bf16>(p.q_pad * D) : nullptr;
+  w.cb_lo = x3 ? cv.take<__bf16>(p.c_pad * D) : nullptr;
+  w.bias_logq = cv.take<float>(p.c_pad);
+  w.bias_lse = cv.take<float>(p.q_pad);
+  w.part_m = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
+  w.part_l = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
+  w.part_o_rows = cv.take<float>(int64_t(p.rows.split) * p.q_pad * D);
+  w.part_o_cols = cv.take<float>(int64_t(p.cols.split) * p.c_pad * D);
+  w.ids = hits ? cv.take<int32_t>(p.c_pad) : nullptr;
+  w.thr = hard ? cv.take<float>(p.q_pad) : nullptr;
+  return w;
+}
+}  // namespace
+}  // namespace tt
+
+extern "C" size_t tt_inbatch_fused_mixed_workspace_size(int64_t n, int64_t m, int32_t dim, int32_t x3) {
+  if (n < 1 || m < 0 || pick_dpad(dim) == 0) return 0;
+  Carver cv(nullptr, 0);
+  carve_fused(cv, fused_plan(n, dim), x3 != 0, true, true);  // m = 0: the square entry's
+  const size_t sq = cv.used();
+  if (m == 0) return sq;
+  Carver cm(nullptr, 0);
+  carve_mixed(cm, mixed_plan(n, m, dim), x3 != 0, true, true);
+  return cm.used() > sq ? cm.used() : sq;
+}
+
+extern "C" int tt_inbatch_softmax_xent_mixed(const float* q, int64_t ldq, int64_t n, const float* c, int64_t ldc,
+                                             int64_t m, int32_t dim, const float* logq, const int32_t* ids,
+                                             int32_t x3, int64_t k, float* lse, float* row_loss, float* dq,
+                                             float* dc, float* thr, float loss_scale, float* loss, void* workspace,
+                                             size_t workspace_bytes, tt_stream_t stream) {
+  using namespace tt;
+  clear_error();
+  const char* fn = "tt_inbatch_softmax_xent_mixed";
+  TT_REQUIRE(m >= 0, "%s: m must be >= 0", fn);
+  TT_REQUIRE(k >= 0, "%s: k must be >= 0 (0: no mining)", fn);
+  TT_REQUIRE(k == 0 || thr, "%s: NULL thr", fn);
+  if (m == 0)
+    return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
+                        loss_scale, loss, x3 != 0, ids, k, thr);
+  int rc = check_common(q, ldq, n, c, ldc, n + m, dim);
+  if (rc) return rc;
+  TT_REQUIRE(lse && row_loss && dq && dc, "%s: NULL output", fn);
+  const bool X3 = x3 != 0, hard = k > 0;
+  const MixedPlan p = mixed_plan(n, m, dim);
+  const int D = p.rows.D;
+  Carver cv(workspace, workspace_bytes);
+  MixedWs w = carve_mixed(cv, p, X3, ids != nullptr, hard);
+  if (!workspace || cv.used() > workspace_bytes)
+    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
+  hipStream_t st = to_stream(stream);
+  const PrepJob none{};
+  // q's job leaves -inf on the padded rows of the cols pass's bias (-lse;
+  // its [0, n) comes from the rows combine), c's job writes -logq and the ids
+  PrepJob jq = prep_job(q, ldq, n, dim, w.qb, nullptr, w.bias_lse);
+  PrepJob jc = prep_job(c, ldc, n + m, dim, w.cb, logq, w.bias_logq);
+  jq.dst_lo = w.qb_lo;
+  jc.dst_lo = w.cb_lo;
+  jc.ids = ids, jc.ids_dst = w.ids;  // one padded copy: row i's id is column i's
+  if ((rc = prep(D, jq, none, dim, p.q_pad, st))) return rc;
+  if ((rc = prep(D, jc, none, dim, p.c_pad, st))) return rc;
+  if (hard) {
+    const SelectArgs sel{w.qb, w.cb, w.bias_logq, n, p.rows.strm_pad, 0, w.qb_lo, w.cb_lo, w.ids, w.ids, clamp_k(k),
+                         thr, w.thr};
+    if ((rc = launch_select(D, p.q_pad, sel, X3, st))) return rc;
+  }
+  PassArgs ar{w.qb, w.cb, w.bias_logq, p.q_pad, p.rows.strm_pad, p.rows.per_split, 0, w.part_m, w.part_l,
+              w.part_o_rows, w.qb_lo, w.cb_lo, w.ids, w.ids, w.thr, nullptr};
+  if ((rc = launch_pass_any<0>(p.rows, ar, X3, st))) return rc;
+  if ((rc = combine_rows(D, st, w.part_m, w.part_l, w.part_o_rows, p.rows.split, p.q_pad, q, ldq, c, ldc, logq, n,
+                         dim, 0, lse, row_loss, dq, w.bias_lse)))
+    return rc;
+  PassArgs ac{w.cb, w.qb, w.bias_lse, p.c_pad, p.cols.strm_pad, p.cols.per_split, 0, nullptr, nullptr,
+              w.part_o_cols, w.cb_lo, w.qb_lo, w.ids, w.ids, w.thr, w.bias_logq};
+  if ((rc = launch_pass_any<1>(p.cols, ac, X3, st))) return rc;
+  return combine_cols_mixed(D, st, w.part_o_cols, p.cols.split, p.c_pad, q, ldq, c, ldc, lse, row_loss, logq, n + m,
+                            dim, 0, dc, n, loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
 }

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 __all__ = [
     "LIB_PATH",
@@ -403,6 +403,18 @@ _PROTOS = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p,
          c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "tt_inbatch_mixed_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "tt_inbatch_xent_cols_mixed": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "tt_inbatch_fused_mixed_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "tt_inbatch_softmax_xent_mixed": (
+        c_int32,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "tt_bruteforce_index_bytes": (c_size_t, [c_int64, c_int32]),
     "tt_bruteforce_build": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "tt_bruteforce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
@@ -459,6 +471,10 @@ _PROTOS = {
         c_int32,
         [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
          c_void_p]),
+    "tt_mixed_candidates": (
+        c_int32,
+        [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_uint64, c_void_p, c_void_p, c_int64,
+         c_void_p, c_void_p]),
     "tt_l2norm_rows": (c_int32, [c_void_p, c_int32, c_void_p]),
     "tt_l2norm_rows_grad": (c_int32, [c_void_p, c_int32, c_void_p]),
     "tt_gather_bag": (c_int32, [POINTER(BagJob), c_int32, c_int64, c_void_p]),

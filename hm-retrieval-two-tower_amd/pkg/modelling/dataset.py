@@ -24,7 +24,8 @@ from pkg.schema.features import Feature
 from pkg.modelling.device import default_device
 from pkg.modelling import hip_ops
 
-__all__ = ["EncodedDataset", "DeviceDataset", "EncodedColumns", "encode_dataframe", "epoch_order", "WEIGHT_KEY"]
+__all__ = ["EncodedDataset", "DeviceDataset", "EncodedColumns", "CandidateCatalogue", "encode_dataframe",
+           "epoch_order", "WEIGHT_KEY"]
 
 # per-example sample weights, normalised to [0, 1] (two_tower_model.WEIGHT_KEY)
 WEIGHT_KEY = "__weight__"
@@ -356,3 +357,69 @@ class DeviceDataset:
         for s in range(0, self.num_rows, bs):
             batch = self.view(self.take(min(bs, self.num_rows - s)))
             yield self.fn(batch) if self.fn else batch
+
+
+class CandidateCatalogue:
+    """The whole candidate catalogue, one row per candidate, resident on the
+    device: what mixed negative sampling draws its extra negatives from
+    (TwoTowerModel(num_sampled_negatives=M), set_candidate_catalogue).
+
+    Every candidate feature is one row of `words`, an int32 [F, N] matrix of
+    32-bit words in the order of candidate_features (int32 embedding rows of a
+    categorical feature, the bits of the float32 values of a numeric one):
+    DeviceDataset's layout, so a step's B + M candidates are assembled by one
+    launch (tt_mixed_candidates).  Plain construction takes already encoded
+    columns ({feature name: [N] array}); from_dataframe encodes raw values
+    with the features' own vocabularies.  A sequence feature is refused."""
+
+    def __init__(self, columns: Dict[str, np.ndarray], candidate_features: Sequence[Feature],
+                 device: Optional[torch.device] = None):
+        self._refuse_sequences(candidate_features)
+        feats = list({f.name: f for f in candidate_features}.values())
+        self.feature_names: List[str] = [f.name for f in feats]
+        self._is_int = [f.dtype == dtypes.string for f in feats]
+        missing = [n for n in self.feature_names if n not in columns]
+        if missing:
+            raise ValueError(f"the catalogue lacks the candidate feature(s) {missing}")
+        words = []
+        for f in feats:
+            v = np.asarray(columns[f.name]).reshape(-1)
+            if f.dtype == dtypes.string:
+                if v.dtype.kind not in "iu":
+                    raise TypeError(f"column {f.name} must hold encoded int rows (got {v.dtype}); "
+                                    "CandidateCatalogue.from_dataframe encodes raw values")
+                if v.size and (v.min() < 0 or v.max() > len(f.vocab)):
+                    raise ValueError(f"column {f.name} holds rows outside [0, {len(f.vocab)}]")
+                words.append(np.ascontiguousarray(v, dtype=np.int32))
+            else:
+                words.append(np.ascontiguousarray(v, dtype=np.float32).view(np.int32))
+        lens = {len(w) for w in words}
+        if len(lens) != 1 or not min(lens):
+            raise ValueError(f"the catalogue's columns must be non-empty and of one length, got {sorted(lens)}")
+        self.num_rows = lens.pop()
+        if self.num_rows >= 1 << 31:
+            raise ValueError(f"a catalogue of {self.num_rows} rows is beyond the sampler's 2^31")
+        self.device = device if device is not None else default_device()
+        self.words = torch.from_numpy(np.stack(words)).to(self.device)
+
+    @staticmethod
+    def _refuse_sequences(candidate_features: Sequence[Feature]) -> None:
+        for f in candidate_features:
+            if getattr(f, "is_sequence", False):
+                raise NotImplementedError(f"CandidateCatalogue does not hold sequence features (feature {f.name!r}, "
+                                          f"sequence_length={f.sequence_length})")
+
+    @classmethod
+    def from_dataframe(cls, df: pd.DataFrame, candidate_features: Sequence[Feature],
+                       device: Optional[torch.device] = None) -> "CandidateCatalogue":
+        """One row per row of df, encoded as encode_dataframe encodes a batch."""
+        cls._refuse_sequences(candidate_features)
+        return cls(encode_dataframe(df, candidate_features), candidate_features, device)
+
+    def __len__(self) -> int:
+        return self.num_rows
+
+    def column(self, name: str) -> torch.Tensor:
+        """Feature `name`'s [N] device column (int32 rows or float32 values)."""
+        f = self.feature_names.index(name)
+        return self.words[f] if self._is_int[f] else self.words[f].view(torch.float32)

@@ -920,6 +920,9 @@ class ShardedTrainStep:
             if getattr(f, "is_sequence", False):
                 raise NotImplementedError(f"ShardedTrainStep does not support sequence features (feature {f.name!r}, "
                                           f"sequence_length={f.sequence_length})")
+        if getattr(model, "num_sampled_negatives", None) is not None:
+            raise NotImplementedError("ShardedTrainStep does not support mixed negative sampling "
+                                      f"(num_sampled_negatives={model.num_sampled_negatives}); train single-device")
         opt = model.optimizer
         if not isinstance(opt, Adagrad):
             raise NotImplementedError("ShardedTrainStep supports the Adagrad optimizer")

@@ -132,7 +132,10 @@ def save_two_tower(model, path_noext: str) -> None:
             "candidate_tower_units": model.candidate_tower.hidden_units,
             "remove_accidental_hits": bool(model.remove_accidental_hits),
             "normalize_embeddings": bool(model.normalize_embeddings), "temperature": model.temperature,
-            "num_hard_negatives": model.num_hard_negatives}
+            "num_hard_negatives": model.num_hard_negatives,
+            # mixed negative sampling: the setting and its seed (the catalogue itself is not saved)
+            "num_sampled_negatives": model.num_sampled_negatives,
+            "sampled_negatives_seed": model.sampled_negatives_seed}
     arrays = _vocab_arrays(model.query_features, "query.")
     arrays.update(_vocab_arrays(model.candidate_features, "candidate."))
     arrays["logq.keys"] = np.asarray(list(lookup.keys()), dtype=str)
@@ -155,7 +158,9 @@ def load_two_tower(path_noext: str, device=None):
                           remove_accidental_hits=bool(meta.get("remove_accidental_hits", False)),
                           normalize_embeddings=bool(meta.get("normalize_embeddings", False)),
                           temperature=meta.get("temperature"),
-                          num_hard_negatives=meta.get("num_hard_negatives"))
+                          num_hard_negatives=meta.get("num_hard_negatives"),
+                          num_sampled_negatives=meta.get("num_sampled_negatives"),
+                          sampled_negatives_seed=int(meta.get("sampled_negatives_seed", 0)))
     model.query_tower.load_state_dict({k[len("query_tower."):]: v for k, v in tensors.items()
                                        if k.startswith("query_tower.")})
     model.candidate_tower.load_state_dict({k[len("candidate_tower."):]: v for k, v in tensors.items()

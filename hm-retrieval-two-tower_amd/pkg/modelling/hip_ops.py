@@ -34,6 +34,8 @@ __all__ = [
     "inbatch_cols",
     "inbatch_weight_rows",
     "inbatch_fused",
+    "inbatch_fused_mixed",
+    "mixed_candidates",
     "inbatch_fused_workspace",
     "inbatch_prep",
     "l2norm_rows",
@@ -929,14 +931,17 @@ def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool
 def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
                  pos_offset: int = 0, row_loss: Optional[torch.Tensor] = None, x3: bool = False,
                  row_ids: Optional[torch.Tensor] = None, col_ids: Optional[torch.Tensor] = None,
-                 thr: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 thr: Optional[torch.Tensor] = None, mixed: bool = False) -> torch.Tensor:
     """Column pass: dc [C,E] from every row's q [R,E], lse [R] and (optional,
     for the exact 1 - P_pos of confident rows) row_loss [R].  x3: fp32-faithful
     products (tt_inbatch_xent_cols_x3).  row_ids [R], col_ids [C] (int32, both
     or neither): accidental hits removed as in inbatch_rows, whose lse and
     row_loss must come from the same ids (tt_inbatch_xent_cols_hits).
     thr [R]: every row's hard-negative threshold, the one its lse came from
-    (tt_inbatch_xent_cols_hard)."""
+    (tt_inbatch_xent_cols_hard).  mixed: columns whose positive row j +
+    pos_offset falls outside [0, R) are extra negatives of every row with no
+    positive term (tt_inbatch_xent_cols_mixed; ids and thr as above, or
+    none)."""
     hits = _ids_pair(row_ids, col_ids, q, c)
     _req(q, "q", torch.float32, 2)
     _req(c, "c", torch.float32, 2)
@@ -945,6 +950,16 @@ def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Opti
     C = c.shape[0]
     L = lib()
     dc = torch.empty(C, E, dtype=torch.float32, device=q.device)
+    if mixed:
+        rid, cid = hits if hits is not None else (None, None)
+        ws = Workspace.get(L.tt_inbatch_mixed_workspace_size(R, C, E, int(x3)), q.device,
+                           "inbatch_mixed_x3" if x3 else "inbatch_mixed")
+        check(L.tt_inbatch_xent_cols_mixed(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
+                                           _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
+                                           _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3),
+                                           _opt_ptr(thr, "thr", R), dc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _stream()))
+        return dc
     if thr is not None:
         rid, cid = hits if hits is not None else (None, None)
         ws = _hard_workspace(L, R, C, E, q.device, x3)
@@ -1110,6 +1125,44 @@ def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor]
     check(fn(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B), lse.data_ptr(), row_loss.data_ptr(),
              dq.data_ptr(), dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return lse, row_loss, dq, dc
+
+
+def inbatch_fused_mixed(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
+                        loss_scale: Optional[float] = None, x3: bool = False, ids: Optional[torch.Tensor] = None,
+                        hard_k: Optional[int] = None):
+    """inbatch_fused with extra negatives (tt_inbatch_softmax_xent_mixed):
+    q [B, E] against c [B + M, E], row i's positive column i, columns past B
+    negatives of every row (mixed negative sampling).  logq and ids have
+    B + M entries.  Returns (lse [B], row_loss [B], dq [B, E], dc [B + M, E]
+    [, thr [B] with hard_k][, loss with loss_scale]); M = 0 is inbatch_fused."""
+    if hard_k is not None:
+        hard_k = _hard_k(hard_k)
+    idp = _ids_ptr(ids, "ids", c) if ids is not None else None
+    _req(q, "q", torch.float32, 2)
+    _req(c, "c", torch.float32, 2)
+    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
+    B, E = q.shape
+    M = c.shape[0] - B
+    if c.shape[1] != E or M < 0:
+        raise ValueError(f"c must be [B + M, E] with M >= 0 for q [B, E], got {tuple(c.shape)} for {tuple(q.shape)}")
+    L = lib()
+    ws = Workspace.get(L.tt_inbatch_fused_mixed_workspace_size(B, M, E, int(x3)), q.device,
+                       "inbatch_fused_mixed_x3" if x3 else "inbatch_fused_mixed")
+    lse = torch.empty(B, dtype=torch.float32, device=q.device)
+    row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
+    dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
+    dc = torch.empty(B + M, E, dtype=torch.float32, device=q.device)
+    thr = torch.empty(B, dtype=torch.float32, device=q.device) if hard_k is not None else None
+    loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
+    check(L.tt_inbatch_softmax_xent_mixed(q.data_ptr(), ldq, B, c.data_ptr(), ldc, M, E,
+                                          _opt_ptr(logq, "logq", B + M), idp, int(x3), hard_k or 0, lse.data_ptr(),
+                                          row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(),
+                                          thr.data_ptr() if thr is not None else None,
+                                          float(loss_scale if loss_scale is not None else 1.0),
+                                          loss.data_ptr() if loss is not None else None, ws.data_ptr(), ws.numel(),
+                                          _stream()))
+    out = (lse, row_loss, dq, dc) + ((thr,) if thr is not None else ()) + ((loss,) if loss is not None else ())
+    return out
 
 
 # --------------------------------------------------------------------------
@@ -1351,6 +1404,44 @@ def batch_take(src: torch.Tensor, perm: torch.Tensor, cursor: torch.Tensor, out:
                               cursor.data_ptr(), out.shape[1], int(bool(advance)), out.data_ptr(),
                               _row_major(out, "out"), status.data_ptr() if status is not None else None,
                               _stream()))
+    return out
+
+
+def mixed_candidates(batch_cols: Sequence[torch.Tensor], cat: torch.Tensor, m: int, seed: int, step: torch.Tensor,
+                     out: torch.Tensor, status: Optional[torch.Tensor] = None, n_cat: Optional[int] = None
+                     ) -> torch.Tensor:
+    """Mixed negative sampling, the candidate side of one step
+    (tt_mixed_candidates): out[f, :B] = batch_cols[f], out[f, B + j] =
+    cat[f, s_j] with the m rows s_j drawn uniformly from the catalogue's
+    n_cat rows (default: all of cat's) by Philox4x32-10 at (seed, *step).
+    batch_cols: one contiguous [B] column of 32-bit words (int32 / float32)
+    per catalogue column; cat, out: int32 [F, N] / [F, >= B + m]; step: device
+    int64 [1], left at step + 1.  Graph-capturable: nothing is read on the
+    host, and every replay draws fresh rows."""
+    _req(cat, "cat", torch.int32, 2)
+    _req(out, "out", torch.int32, 2)
+    _req(step, "step", torch.int64, 1)
+    F = cat.shape[0]
+    if len(batch_cols) != F or out.shape[0] != F:
+        raise ValueError(f"the catalogue has {F} columns, the batch {len(batch_cols)}, out {out.shape[0]}")
+    B = batch_cols[0].numel()
+    for i, t in enumerate(batch_cols):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.float32):
+            raise TypeError(f"batch column {i} must be an int32 or float32 tensor")
+        if t.dim() != 1 or t.numel() != B or not t.is_contiguous() or t.device != cat.device:
+            raise ValueError(f"batch column {i} must be a contiguous [{B}] tensor on {cat.device}")
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"m={m} must be >= 1")
+    if out.shape[1] < B + m:
+        raise ValueError(f"out has {out.shape[1]} slots for {B} + {m}")
+    if status is not None:
+        _req(status, "status", torch.int32, 1)
+    ptrs = (ctypes.c_void_p * F)(*[t.data_ptr() for t in batch_cols])
+    check(lib().tt_mixed_candidates(ptrs, cat.data_ptr(), _row_major(cat, "cat"), F, B, m,
+                                    cat.shape[1] if n_cat is None else int(n_cat), int(seed) & (2 ** 64 - 1),
+                                    step.data_ptr(), out.data_ptr(), _row_major(out, "out"),
+                                    status.data_ptr() if status is not None else None, _stream()))
     return out
 
 

@@ -75,6 +75,20 @@ def x3_scores() -> bool:
 # issued.
 
 
+# Extra negatives (the single-device losses below): c may have more rows than
+# q.  Rows past len(q) are negatives of every row and positives of none — the
+# candidates mixed negative sampling draws from the whole catalogue
+# (TwoTowerModel(num_sampled_negatives=M)); logq and ids then have len(c)
+# entries, ids[i] being row i's id as well.  The rows pass and the selection
+# take the wider c as they are, the cols pass is its MIXED form (include/tt.h,
+# "mixed negatives").  c with len(q) rows issues the calls it always issued.
+
+
+def _row_ids(ids, q):
+    """The rows' ids of a loss whose ids cover every column: the first len(q)."""
+    return None if ids is None else ids[:q.shape[0]]
+
+
 def _check_hard(k):
     if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
         raise ValueError(f"num_hard_negatives must be a positive int or None, got {k!r}")
@@ -87,6 +101,16 @@ def weighted_inbatch_grads(q, c, logq, weights, ids=None, x3: Optional[bool] = N
     cols, with the operands and ids the unweighted entries take;
     num_hard_negatives: select, rows, fold, cols."""
     x3 = x3_scores() if x3 is None else x3
+    if c.shape[0] != q.shape[0]:  # extra negatives: (select,) rows, fold, the MIXED cols pass
+        rid = _row_ids(ids, q)
+        thr = None
+        if _check_hard(num_hard_negatives) is not None:
+            thr = hip_ops.inbatch_hard_threshold(q, c, logq, num_hard_negatives, x3=x3, row_ids=rid, col_ids=ids)
+        lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=rid, col_ids=ids, thr=thr)
+        lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
+        dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=rid, col_ids=ids, thr=thr,
+                                  mixed=True)
+        return wloss, dq, dc
     if _check_hard(num_hard_negatives) is None:
         lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids)
         lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
@@ -105,6 +129,8 @@ class _InBatchXent(torch.autograd.Function):
         if weights is not None:
             scale = scale * weight_scale
             row_loss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
+        elif c.shape[0] != q.shape[0]:  # extra negatives
+            _, row_loss, dq, dc = hip_ops.inbatch_fused_mixed(q, c, logq, x3=x3_scores(), ids=ids, hard_k=hard)[:4]
         elif hard is not None:
             _, row_loss, dq, dc, _ = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids, hard_k=hard)
         else:
@@ -250,7 +276,8 @@ class _TowersInBatchXent(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None,
                 weights=None, weight_scale=1.0, hard=None):
-        ctx.pair = _paired(qi, stack_q, stack_c)
+        # (extra negatives: the candidate tower runs on more rows, the towers unpaired)
+        ctx.pair = _paired(qi, stack_q, stack_c) and qi.shape[0] == ci.shape[0]
         ctx.on_dx = on_dx
         if ctx.pair:
             qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
@@ -263,7 +290,7 @@ class _TowersInBatchXent(torch.autograd.Function):
         # (not under x3_scores() or with ids: those entries prepare their operands themselves;
         # not with normalised outputs: it would prepare the un-normalised ones)
         split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None and hard is None
-                      and not (stack_q.normalize or stack_c.normalize))
+                      and not (stack_q.normalize or stack_c.normalize) and qi.shape[0] == ci.shape[0])
         ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
         side.wait_stream(main)
         with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
@@ -293,6 +320,9 @@ class _TowersInBatchXent(torch.autograd.Function):
         if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
             wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
             loss = hip_ops.loss_sum(wloss, scale)
+        elif c.shape[0] != q.shape[0]:  # extra negatives (its own preparation and workspace), every option
+            out = hip_ops.inbatch_fused_mixed(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids, hard_k=hard)
+            dq, dc, loss = out[2], out[3], out[-1]
         elif hard is not None:  # hard negatives (its own preparation and workspace), either arithmetic, ids or none
             _, _, dq, dc, _, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids,
                                                           hard_k=hard)
@@ -370,6 +400,9 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     as a keyword, thr joins the all-gather of [lse, row_loss] as a third
     column, and the cols pass takes every row's thr= (injected rows / cols
     receive it as a keyword)."""
+    if c.shape[0] != q.shape[0]:
+        raise NotImplementedError(f"global_inbatch_grads: c has {c.shape[0]} rows for {q.shape[0]} rows of q; extra "
+                                  "negatives (mixed negative sampling) are single-device only")
     if x3 is None:
         x3 = x3_scores()
     hard = _check_hard(num_hard_negatives)
@@ -503,6 +536,7 @@ def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
                          num_hard_negatives: Optional[int] = None) -> torch.Tensor:
     """Loss of query rows q [B,E] against candidates c [B,E] (positive of row
     i is column i), logq [B] the per-candidate log sampling probability.
+    c [B + M, E]: rows past B are extra negatives of every row (see above).
     ids [B] (int32): accidental hits removed (see above).  weights [B] (fp32,
     in [0, 1]) and weight_scale: sample weights (see above).
     num_hard_negatives: hard-negative mining (see above)."""
@@ -512,12 +546,13 @@ def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     hard = _check_hard(num_hard_negatives)
     if not q.requires_grad and not c.requires_grad:
         # the scores the training loss is computed from, in either mode
+        rid = ids if c.shape[0] == q.shape[0] else _row_ids(ids, q)  # (extra negatives: the rows entries as they are)
         if hard is not None:
-            thr = hip_ops.inbatch_hard_threshold(q, c, logq, hard, x3=x3_scores(), row_ids=ids, col_ids=ids)
-            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids,
+            thr = hip_ops.inbatch_hard_threshold(q, c, logq, hard, x3=x3_scores(), row_ids=rid, col_ids=ids)
+            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=rid,
                                                     col_ids=ids, thr=thr)
         else:
-            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=ids,
+            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=rid,
                                                     col_ids=ids)
         if weights is not None:
             _, _, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss)

@@ -23,6 +23,7 @@ from typing import Any, Dict, Iterable, List, Optional
 import numpy as np
 import torch
 
+from pkg import dtypes as _dtypes
 from pkg.schema.features import Feature
 from pkg.schema.schema import Schema
 from pkg.modelling.device import default_device, make_generator
@@ -115,6 +116,25 @@ class TwoTowerModel(AbstractKerasModel):
         step path; negatives that tie the K-th logit are all kept.  K at or
         above the batch size is the default loss bit for bit.  Anything but
         a positive int raises ValueError.
+    num_sampled_negatives: Optional[int]
+        None (the default): the negatives are the batch's other candidates.
+        A positive int M: mixed negative sampling (Yang et al. 2020) — every
+        TRAINING step scores the B queries against B + M columns, the batch's
+        candidates followed by M rows drawn uniformly with replacement, fresh
+        on every step, from the catalogue attached with
+        set_candidate_catalogue.  The extra columns are negatives of every
+        row; their embeddings come from the candidate tower and their
+        gradient flows back into it and its tables.  With a
+        candidate_prob_lookup the logQ shift of a column holding embedding
+        row r is the mixture's, log((B p_r + M / N) / (B + M)), N the
+        catalogue size.  Evaluation (compute_loss(training=False)) stays the
+        plain in-batch loss.  With remove_accidental_hits a sampled column
+        holding a row's own positive is masked for that row; without it such
+        a column is a negative (one warning is logged).  Anything but a
+        positive int raises ValueError.  Single-device only.
+    sampled_negatives_seed: int
+        Seed of the sampler (Philox4x32-10 keyed by it, counted by the
+        model's device step counter).
     """
 
     def __init__(self, query_features: List[Feature], candidate_features: List[Feature], candidate_id_col: str,
@@ -124,7 +144,22 @@ class TwoTowerModel(AbstractKerasModel):
                  device: Optional[torch.device] = None, seed: Optional[int] = None,
                  fused_optimizer_apply: bool = False, remove_accidental_hits: bool = False,
                  normalize_embeddings: bool = False, temperature: Optional[float] = None,
-                 num_hard_negatives: Optional[int] = None):
+                 num_hard_negatives: Optional[int] = None, num_sampled_negatives: Optional[int] = None,
+                 sampled_negatives_seed: int = 0):
+        if num_sampled_negatives is not None and (isinstance(num_sampled_negatives, bool)
+                                                  or not isinstance(num_sampled_negatives, (int, np.integer))
+                                                  or num_sampled_negatives < 1):
+            raise ValueError(f"num_sampled_negatives={num_sampled_negatives!r} must be a positive int or None")
+        if isinstance(sampled_negatives_seed, bool) or not isinstance(sampled_negatives_seed, (int, np.integer)):
+            raise ValueError(f"sampled_negatives_seed={sampled_negatives_seed!r} must be an int")
+        self.num_sampled_negatives = None if num_sampled_negatives is None else int(num_sampled_negatives)
+        self.sampled_negatives_seed = int(sampled_negatives_seed)
+        self.candidate_catalogue = None
+        self._mixed_buffers: Dict[int, torch.Tensor] = {}   # B -> the assembled [F, B + M] candidate words
+        self._mixed_logq: Dict[tuple, torch.Tensor] = {}    # (B, M) -> the mixture's logQ per embedding row
+        self._mixed_step: Optional[torch.Tensor] = None     # the sampler's step counter (device int64 [1])
+        self._mixed_status: Optional[torch.Tensor] = None
+        self._mixed_warned = False
         if num_hard_negatives is not None and (isinstance(num_hard_negatives, bool)
                                                or not isinstance(num_hard_negatives, (int, np.integer))
                                                or num_hard_negatives < 1):
@@ -249,7 +284,120 @@ class TwoTowerModel(AbstractKerasModel):
         out = torch.empty(ids.numel(), 1, dtype=torch.float32, device=self.device)
         return [(self._logq_rows.view(-1, 1), ids, 0)], out
 
+    # ------------------------------------------------------------------ mixed negative sampling
+    def set_candidate_catalogue(self, catalogue) -> None:
+        """Attach the pkg.modelling.dataset.CandidateCatalogue the M extra
+        negatives of a training step are drawn from (num_sampled_negatives).
+        It must hold the candidate tower's features; it is not saved with the
+        model.  Attaching one restarts the sampler at step 0."""
+        from pkg.modelling.dataset import CandidateCatalogue
+
+        if catalogue is not None:
+            if not isinstance(catalogue, CandidateCatalogue):
+                raise TypeError("set_candidate_catalogue takes a pkg.modelling.dataset.CandidateCatalogue")
+            seq = [f.name for f in self.candidate_features if f.is_sequence]
+            if seq:
+                raise NotImplementedError(f"mixed negative sampling does not support sequence features in the "
+                                          f"candidate tower (feature {seq[0]!r})")
+            want = list(dict.fromkeys(f.name for f in self.candidate_features))
+            if catalogue.feature_names != want:
+                raise ValueError(f"the catalogue holds {catalogue.feature_names}, the candidate tower takes {want}")
+            if catalogue.words.device != self.device:
+                raise ValueError(f"the catalogue lives on {catalogue.words.device}, the model on {self.device}")
+        self.candidate_catalogue = catalogue
+        self._mixed_buffers, self._mixed_logq = {}, {}
+        self._mixed_step = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._mixed_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._device_fit_graph = None  # a cached fit graph holds the old catalogue's addresses
+
+    def _warn_mixed_hits(self) -> None:
+        if self.num_sampled_negatives is not None and not self.remove_accidental_hits and not self._mixed_warned:
+            self._mixed_warned = True
+            logger.warning("num_sampled_negatives is set without remove_accidental_hits: a sampled candidate equal to "
+                           "a row's own positive is scored as a negative of that row")
+
+    def mixture_logq_table(self, batch_size: int) -> torch.Tensor:
+        """The mixture's logQ per embedding row r of the candidate-id feature
+        at this batch size: log((B p_r + M / N) / (B + M)), p_r the lookup's
+        (fp32) probability of vocab[r - 1], 1 for rows outside the lookup (the
+        reference's rule, the OOV row 0 included), N the catalogue size.
+        Built on the host in fp64, rounded to fp32, cached per (B, M)."""
+        B, M, N = int(batch_size), self.num_sampled_negatives, self.candidate_catalogue.num_rows
+        key = (B, M)
+        if key not in self._mixed_logq:
+            feat = next(f for f in self.candidate_features if f.name == self.candidate_id_col)
+            keys = list(self.logq_correction.lookup.keys())
+            rows = feat.encode(np.asarray(keys, dtype=str)) if keys else np.zeros(0, np.int64)
+            if np.any(rows == 0):
+                missing = [k for k, r in zip(keys, rows.tolist()) if r == 0][:3]
+                raise ValueError(f"candidate_prob_lookup has ids outside the {feat.name} vocab (e.g. {missing}); "
+                                 "mixed negative sampling reads logQ by embedding row")
+            p = np.ones(len(feat.vocab) + 1, np.float64)
+            p[rows] = np.asarray(list(self.logq_correction.lookup.values()), np.float32).astype(np.float64)
+            table = np.log((B * p + M / N) / (B + M)).astype(np.float32)
+            self._mixed_logq[key] = torch.as_tensor(table, device=self.device)
+        return self._mixed_logq[key]
+
+    def _compute_loss_mixed(self, x: Dict[str, Any]) -> torch.Tensor:
+        """The training loss with num_sampled_negatives: the candidate side
+        sampled and assembled by one tt_mixed_candidates launch into a
+        persistent [F, B + M] buffer (so a captured step replays it), each
+        tower gathered by its own launch (the logQ lookup rides with the
+        candidate tower's), then the loss over B rows and B + M columns."""
+        cat, M = self.candidate_catalogue, self.num_sampled_negatives
+        if cat is None:
+            raise RuntimeError(f"num_sampled_negatives={M} needs a candidate catalogue: call "
+                               "set_candidate_catalogue(CandidateCatalogue...) before training")
+        if LOGQ_KEY in x:
+            raise ValueError(f"a batch carrying {LOGQ_KEY!r} cannot train with num_sampled_negatives: the sampled "
+                             "columns have no such value (logQ is read by embedding row)")
+        self._warn_mixed_hits()
+        q, c = self._split(x)
+        layer = self.candidate_tower.input_layer
+        feats = {f.name: f for f in self.candidate_features}
+        cols = []
+        for name in cat.feature_names:
+            f = feats[name]
+            if f.dtype == _dtypes.string:
+                cols.append(layer._ids(c[name], f))
+            else:
+                v = c[name] if isinstance(c[name], torch.Tensor) else torch.as_tensor(np.asarray(c[name], np.float32))
+                cols.append(v.reshape(-1).to(device=self.device, dtype=torch.float32).contiguous())
+        B = cols[0].numel()
+        buf = self._mixed_buffers.get(B)
+        if buf is None:
+            buf = self._mixed_buffers[B] = torch.empty(len(cols), B + M, dtype=torch.int32, device=self.device)
+        hip_ops.mixed_candidates(cols, cat.words, M, self.sampled_negatives_seed, self._mixed_step, buf,
+                                 self._mixed_status)
+        cm = {name: (buf[i] if feats[name].dtype == _dtypes.string else buf[i].view(torch.float32))
+              for i, name in enumerate(cat.feature_names)}
+        ids_all = cm[self.candidate_id_col]
+        with torch.enable_grad():
+            call = None
+            if self.logq_correction is not None:
+                out = torch.empty(B + M, 1, dtype=torch.float32, device=self.device)
+                call = ([(self.mixture_logq_table(B).view(-1, 1), ids_all, 0)], out)
+            pack = []
+            if PACK_WITH_GATHER and self.device.type == "cuda":
+                pack = [j for t in self.towers for j in t.dense.prepack_jobs(t.dense.flat.detach())]
+                if len(pack) > 8:
+                    for t in self.towers:
+                        t.dense.__dict__["_prepacked"] = None
+                    pack = []
+            (qi,) = InputLayer.gather_many([self.query_tower.input_layer], [q], pack_jobs=pack or None)
+            (ci,) = InputLayer.gather_many([layer], [cm], extra=[call] if call is not None else ())
+            if qi.is_cuda:
+                self._ids_ready = torch.cuda.Event()
+                self._ids_ready.record()
+                if getattr(self, "_on_tower", None) == self._apply_tower:
+                    self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
+            logq = call[1].view(-1) if call is not None else None
+            return self.tower_loss(qi, ci, logq, ids_all if self.remove_accidental_hits else None,
+                                   self.sample_weights(x))
+
     def compute_loss(self, x: Dict[str, Any], training: bool = True) -> torch.Tensor:
+        if training and self.num_sampled_negatives is not None:
+            return self._compute_loss_mixed(x)
         q, c = self._split(x)
         with torch.set_grad_enabled(training):
             call = self._logq_call(x)  # rides in the towers' gather launch
@@ -307,6 +455,7 @@ class TwoTowerModel(AbstractKerasModel):
             self.optimizer = optimizer
             # a cached fit graph holds the old optimizer's slot addresses
             self._device_fit_graph = None
+        self._warn_mixed_hits()
 
     def check_optimizer_status(self) -> None:
         """Raise if a sparse apply since the last check refused stale or
@@ -599,6 +748,8 @@ class GraphedTrainStep:
         self.optimizer = model.optimizer
         # a weighted step (rows, fold, cols, tt_sum) with w_max a constant of the graph
         self.weight_scale = float(model.sample_weight_scale) if WEIGHT_KEY in self.static else None
+        # mixed negative sampling: M and the catalogue whose words the captured sampler reads
+        self.mixed = (model.num_sampled_negatives, model.candidate_catalogue)
         self.ws_snapshot = hip_ops.Workspace.snapshot(owner=self.graph)
 
     def reusable(self, model: "TwoTowerModel", source=None, batch: Optional[Dict[str, Any]] = None) -> bool:
@@ -614,6 +765,8 @@ class GraphedTrainStep:
             return False
         if weighted and self.weight_scale != float(model.sample_weight_scale):
             return False
+        if self.mixed[0] != model.num_sampled_negatives or self.mixed[1] is not model.candidate_catalogue:
+            return False  # captured with another M or catalogue
         return (self.model is model and self.source is source and self.optimizer is model.optimizer
                 and (source is None or int(source.batch_size) == self.batch_size)
                 and hip_ops.Workspace.unchanged(self.ws_snapshot))

@@ -213,7 +213,10 @@ class Adagrad(_Optimizer):
             # accumulators created here are filled on this stream, ahead of
             # anything ordered after the sort
             specs, batch = self._sparse_specs(towers, with_grad=False)
-            if not specs or len(specs) > 16 or not batch:
+            # (towers on different batches — mixed negative sampling runs the
+            # candidate tower on B + M rows — are sorted and applied per tower
+            # by _apply, not presorted here)
+            if not specs or len(specs) > 16 or not batch or not self._one_batch(specs):
                 if specs:  # the apply sorts on `cur`: order it after the accumulator fills
                     cur.wait_stream(side)
                 return
@@ -221,6 +224,11 @@ class Adagrad(_Optimizer):
         done = torch.cuda.Event()
         done.record(side)
         self._prepared = ([id(s["table"]) for s in specs], batch, done)
+
+    @staticmethod
+    def _one_batch(specs) -> bool:
+        """True when every table of `specs` was looked up with the same batch."""
+        return len({s["ids"][0].numel() for s in specs}) <= 1
 
     def _apply(self, towers) -> None:
         lr, eps, init = self.learning_rate, self.epsilon, self.initial_accumulator_value
@@ -233,7 +241,13 @@ class Adagrad(_Optimizer):
         prepared, self._prepared = self._prepared, None
         if prepared is not None:  # join the side stream before anything touches the workspace
             torch.cuda.current_stream().wait_event(prepared[2])
-        if specs:
+        if specs and not self._one_batch(specs):
+            # the towers' batches differ: one sort and one apply per tower
+            for tower in towers:
+                tspecs, tbatch = self._sparse_specs([tower], with_grad=True)
+                if tspecs:
+                    hip_ops.sparse_adagrad(tspecs, tbatch, None, lr, eps)
+        elif specs:
             # every tower's tables in ONE call: one sort, one block pass (each
             # table reads its own tower's input gradient)
             if prepared is None:

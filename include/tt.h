@@ -625,6 +625,56 @@ int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const float* c,
                                  void* workspace, size_t workspace_bytes,
                                  tt_stream_t stream);
 
+/* Opt-in mixed negative sampling (Yang et al., "Mixed Negative Sampling for
+ * Learning Two-tower Neural Networks in Recommendations", 2020): the columns
+ * are the batch's candidates followed by extra candidates, drawn from the
+ * whole catalogue (tt_mixed_candidates), that are negatives of every row.
+ * The reference has no such option; the entries above do not change.
+ *
+ * The rows entries and tt_inbatch_hard_threshold take n_cols > n_rows as they
+ * are.  tt_inbatch_xent_cols_mixed is tt_inbatch_xent_cols_hard without the
+ * rule that every column has a positive row: column j's positive is row
+ * j + pos_offset when that lies in [0, n_rows); otherwise it has none and
+ *
+ *   dc_j = exp(-logq[j]) * sum_i p_ij q_i
+ *
+ * with no positive term and no read of q / lse / row_loss outside [0, n_rows).
+ * row_ids / col_ids (both or neither) and thr may each be NULL: no hits
+ * removed / no mining; x3 as everywhere.  With n_cols + pos_offset <= n_rows
+ * and pos_offset >= 0 every output equals the _cols, _cols_x3, _cols_hits or
+ * _cols_hard entry's bit for bit.  Sample weights compose as before: (select,)
+ * rows, tt_inbatch_weight_rows, tt_inbatch_xent_cols_mixed.
+ *
+ * tt_inbatch_softmax_xent_mixed is the fused single-device form: q [n] rows
+ * against c [n + m] columns, row i's positive column i, columns [n, n + m)
+ * negatives of every row; logq and ids (either may be NULL) have n + m
+ * entries, ids[i] being row i's id too; k = 0: no mining, k >= 1: as
+ * tt_inbatch_softmax_xent_hard (thr [n] returned, NULL allowed for k = 0).
+ * One preparation of each operand, then (select,) rows, cols and the
+ * in-launch *loss (may be NULL).  lse, row_loss, dq (and thr) equal the rows
+ * (and threshold) entries called at n_cols = n + m bit for bit; with m = 0
+ * every output equals the square fused entry's bit for bit. */
+size_t tt_inbatch_mixed_workspace_size(int64_t n_rows, int64_t n_cols,
+                                       int32_t dim, int32_t x3);
+int tt_inbatch_xent_cols_mixed(const float* q, int64_t ldq, int64_t n_rows,
+                               const float* lse, const float* row_loss,
+                               const float* c, int64_t ldc, int64_t n_cols,
+                               int32_t dim, const float* logq,
+                               int64_t pos_offset, const int32_t* row_ids,
+                               const int32_t* col_ids, int32_t x3,
+                               const float* thr, float* dc, void* workspace,
+                               size_t workspace_bytes, tt_stream_t stream);
+size_t tt_inbatch_fused_mixed_workspace_size(int64_t n, int64_t m, int32_t dim,
+                                             int32_t x3);
+int tt_inbatch_softmax_xent_mixed(const float* q, int64_t ldq, int64_t n,
+                                  const float* c, int64_t ldc, int64_t m,
+                                  int32_t dim, const float* logq,
+                                  const int32_t* ids, int32_t x3, int64_t k,
+                                  float* lse, float* row_loss, float* dq,
+                                  float* dc, float* thr, float loss_scale,
+                                  float* loss, void* workspace,
+                                  size_t workspace_bytes, tt_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * K11+K12  Brute-force scoring with fused top-K.
  * Replaces BruteForceIndex.call (pkg/modelling/indices/brute_force.py:76-81):
@@ -820,6 +870,29 @@ int tt_vocab_destroy(void* vocab);
 int tt_batch_take(const void* src, int64_t src_ld, int32_t ncols, const int64_t* perm, int64_t n_rows,
                   int64_t* cursor, int64_t batch, int32_t advance, void* dst, int64_t dst_ld,
                   int32_t* status, tt_stream_t stream);
+
+/* Mixed negative sampling, the candidate side of a step: the batch's `batch`
+ * candidates followed by `m` catalogue rows drawn uniformly with replacement,
+ * sampled and assembled in one pass over dst (32-bit words, column-major):
+ *   dst[f * dst_ld + b]         = batch_cols[f][b]             b < batch
+ *   dst[f * dst_ld + batch + j] = cat[f * cat_ld + s_j]        j < m
+ * batch_cols is a HOST array of ncols (<= 32) device pointers, one [batch]
+ * column each; cat is the catalogue, column-major [ncols][cat_ld] with n_cat
+ * rows.  s_j = (u_j * n_cat) >> 32 with u_j word j & 3 of Philox4x32-10
+ * (multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85) at
+ * counter (j >> 2, step lo, step hi, 0) and key (seed lo, seed hi).  `step`
+ * is an int64 in device memory: every slot of one call sees the same value
+ * and the call leaves step + 1 behind, so the call can be captured and every
+ * replay of the graph draws fresh rows; it synchronises with nothing.
+ * BIAS: the multiply-high mapping sends 2^32 words onto n_cat rows, so a
+ * row's probability is floor or ceil of 2^32 / n_cat over 2^32: it departs
+ * from 1 / n_cat by less than 2^-32, a relative bias of at most n_cat / 2^32
+ * (2.5e-5 at the 105,542 articles of H&M).  n_cat < 1 or n_cat >= 2^31 draws
+ * nothing: the sampled slots get zero words and 1 is ORed into *status
+ * (optional device int32; without it such an n_cat is TT_ERR_BAD_ARG). */
+int tt_mixed_candidates(const void* const* batch_cols, const void* cat, int64_t cat_ld, int32_t ncols,
+                        int64_t batch, int64_t m, int64_t n_cat, uint64_t seed, int64_t* step, void* dst,
+                        int64_t dst_ld, int32_t* status, tt_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * K4  Tower MLP, row-streaming GEMM (Dense layers, pkg/modelling/models/
