@@ -1248,6 +1248,37 @@ Plan make_plan(int64_t n_stat, int64_t n_strm, int dim) {
   return p;
 }
 
+// The options of one call, filled by its extern "C" entry.
+struct Modes {
+  bool x3 = false;                   // bf16x3 products: residual planes beside the bf16 images (X3)
+  const int32_t* row_ids = nullptr;  // both or neither: accidental hits at -inf (HITS); the fused
+  const int32_t* col_ids = nullptr;  // body reads col_ids alone, row i's id being column i's
+  bool hard = false;                 // hard negatives (HARD), either with
+  const float* thr = nullptr;        //   the passes: the rows' thresholds, or
+  int64_t hard_k = 0;                //   the fused body: the negatives kept per row, and
+  float* thr_out = nullptr;          //   where the thresholds it selects go
+  bool mixed = false;                // the cols pass: columns past the rows have no positive (MIXED)
+  bool hits() const { return col_ids != nullptr; }
+};
+
+// The one place where mode booleans and a run-time D (32 / 64 / 128) become
+// template arguments: f(std::bool_constant<flag>..., std::integral_constant<int, D>).
+// (Flags outermost and true first, D innermost: the kernels are instantiated,
+// and so laid out in the code object, in the order they always were.)
+template <typename F>
+int dispatch(int D, F&& f) {
+  switch (D) {
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    default: return f(std::integral_constant<int, 128>{});
+  }
+}
+template <typename F, typename... Bs>
+int dispatch(int D, F&& f, bool flag, Bs... rest) {
+  auto bind = [&](auto c) -> int { return dispatch(D, [&](auto... cs) -> int { return f(c, cs...); }, rest...); };
+  return flag ? bind(std::true_type{}) : bind(std::false_type{});
+}
+
 struct PassWs {
   __bf16* stat;
   __bf16* strm;
@@ -1261,7 +1292,7 @@ struct PassWs {
   float* stat_bias;              // and (cols pass) the stationary columns' -logq
 };
 
-PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false, bool hard = false) {
+PassWs carve_pass(Carver& cv, const Plan& p, bool x3, bool hits, bool hard) {
   PassWs w;
   w.stat = cv.take<__bf16>(p.stat_pad * p.D);
   w.strm = cv.take<__bf16>(p.strm_pad * p.D);
@@ -1279,10 +1310,18 @@ PassWs carve_pass(Carver& cv, const Plan& p, bool x3 = false, bool hits = false,
   return w;
 }
 
-size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3 = false, bool hits = false, bool hard = false) {
+size_t pass_bytes(int64_t n_stat, int64_t n_strm, int dim, bool x3, bool hits, bool hard) {
   Carver cv(nullptr, 0);
   carve_pass(cv, make_plan(n_stat, n_strm, dim), x3, hits, hard);
   return cv.used();
+}
+
+// The rows / cols entries' workspace: the larger of the two passes' carves.
+size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, bool hits = false, bool hard = false) {
+  if (n_rows < 1 || n_cols < 1 || pick_dpad(dim) == 0) return 0;
+  const size_t a = pass_bytes(n_rows, n_cols, dim, x3, hits, hard);
+  const size_t b = pass_bytes(n_cols, n_rows, dim, x3, hits, hard);
+  return a > b ? a : b;
 }
 
 PrepJob prep_job(const float* src, int64_t ld, int64_t n, int dim, __bf16* dst, const float* bv = nullptr,
@@ -1294,76 +1333,40 @@ PrepJob prep_job(const float* src, int64_t ld, int64_t n, int dim, __bf16* dst, 
 // Preps one or two matrices padded to n_pad rows (j1.src == NULL: one).
 int prep(int D, const PrepJob& j0, const PrepJob& j1, int dim, int64_t n_pad, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(n_pad / 32), j1.src ? 2u : 1u);
-  switch (D) {
-    case 32: hipLaunchKernelGGL(prep_kernel<32>, grid, dim3(256), 0, st, j0, j1, dim); break;
-    case 64: hipLaunchKernelGGL(prep_kernel<64>, grid, dim3(256), 0, st, j0, j1, dim); break;
-    default: hipLaunchKernelGGL(prep_kernel<128>, grid, dim3(256), 0, st, j0, j1, dim); break;
-  }
-  TT_CHECK_LAUNCH();
-  return TT_OK;
-}
-
-template <int D>
-void launch_combine_rows(dim3 grid, hipStream_t st, const float* pm, const float* pl, const float* po, int nsplit,
-                         int64_t n_stat_pad, const float* q, int64_t ldq, const float* c, int64_t ldc,
-                         const float* logq, int64_t n, int dim, int64_t pos_offset, float* lse, float* loss,
-                         float* dq, float* neg_lse) {
-  hipLaunchKernelGGL(combine_rows_kernel<D>, grid, dim3(256), 0, st, pm, pl, po, nsplit, n_stat_pad, q, ldq, c, ldc,
-                     logq, n, dim, pos_offset, lse, loss, dq, neg_lse);
+  return dispatch(D, [&](auto d) -> int {
+    hipLaunchKernelGGL(prep_kernel<d()>, grid, dim3(256), 0, st, j0, j1, dim);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+  });
 }
 
 int combine_rows(int D, hipStream_t st, const float* pm, const float* pl, const float* po, int nsplit,
                  int64_t n_stat_pad, const float* q, int64_t ldq, const float* c, int64_t ldc, const float* logq,
                  int64_t n, int dim, int64_t pos_offset, float* lse, float* loss, float* dq, float* neg_lse) {
   const dim3 grid(static_cast<unsigned>(ceil_div(n, 1024 / D)));
-  switch (D) {
-    case 32: launch_combine_rows<32>(grid, st, pm, pl, po, nsplit, n_stat_pad, q, ldq, c, ldc, logq, n, dim,
-                                     pos_offset, lse, loss, dq, neg_lse); break;
-    case 64: launch_combine_rows<64>(grid, st, pm, pl, po, nsplit, n_stat_pad, q, ldq, c, ldc, logq, n, dim,
-                                     pos_offset, lse, loss, dq, neg_lse); break;
-    default: launch_combine_rows<128>(grid, st, pm, pl, po, nsplit, n_stat_pad, q, ldq, c, ldc, logq, n, dim,
-                                      pos_offset, lse, loss, dq, neg_lse); break;
-  }
-  TT_CHECK_LAUNCH();
-  return TT_OK;
+  return dispatch(D, [&](auto d) -> int {
+    hipLaunchKernelGGL(combine_rows_kernel<d()>, grid, dim3(256), 0, st, pm, pl, po, nsplit, n_stat_pad, q, ldq, c,
+                       ldc, logq, n, dim, pos_offset, lse, loss, dq, neg_lse);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+  });
 }
 
+// mixed: the kernel's MIXED form — columns whose positive row j + pos_offset
+// falls outside [0, n_rows) have none.
 int combine_cols(int D, hipStream_t st, const float* po, int nsplit, int64_t n_stat_pad, const float* q,
                  int64_t ldq, const float* c, int64_t ldc, const float* lse, const float* row_loss,
-                 const float* logq, int64_t n, int dim, int64_t pos_offset, float* dc,
-                 const LossSum& loss = LossSum{}) {
+                 const float* logq, int64_t n, int dim, int64_t pos_offset, float* dc, bool mixed, int64_t n_rows,
+                 LossSum loss = LossSum{}) {
   const dim3 grid(static_cast<unsigned>(ceil_div(n, 1024 / D) + (loss.x ? 1 : 0)));
-  switch (D) {
-    case 32: hipLaunchKernelGGL(combine_cols_kernel<32>, grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q, ldq, c,
-                                ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-    case 64: hipLaunchKernelGGL(combine_cols_kernel<64>, grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q, ldq, c,
-                                ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-    default: hipLaunchKernelGGL(combine_cols_kernel<128>, grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q, ldq, c,
-                                ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-  }
-  TT_CHECK_LAUNCH();
-  return TT_OK;
-}
-
-// The MIXED form: columns whose positive row j + pos_offset falls outside
-// [0, n_rows) have none.
-int combine_cols_mixed(int D, hipStream_t st, const float* po, int nsplit, int64_t n_stat_pad, const float* q,
-                       int64_t ldq, const float* c, int64_t ldc, const float* lse, const float* row_loss,
-                       const float* logq, int64_t n, int dim, int64_t pos_offset, float* dc, int64_t n_rows,
-                       const LossSum& loss_in = LossSum{}) {
-  const dim3 grid(static_cast<unsigned>(ceil_div(n, 1024 / D) + (loss_in.x ? 1 : 0)));
-  LossSum loss = loss_in;
-  loss.n = n_rows;  // the MIXED form's n_rows (a loss block sums row_loss [n_rows])
-  switch (D) {
-    case 32: hipLaunchKernelGGL((combine_cols_kernel<32, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
-                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-    case 64: hipLaunchKernelGGL((combine_cols_kernel<64, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
-                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-    default: hipLaunchKernelGGL((combine_cols_kernel<128, true>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
-                                ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss); break;
-  }
-  TT_CHECK_LAUNCH();
-  return TT_OK;
+  if (mixed) loss.n = n_rows;  // the MIXED form's n_rows (a loss block sums row_loss [n_rows])
+  // (dispatched on "every column has a positive": the default form comes first in the code object)
+  return dispatch(D, [&](auto ALL_POS, auto d) -> int {
+    hipLaunchKernelGGL((combine_cols_kernel<d(), !ALL_POS()>), grid, dim3(256), 0, st, po, nsplit, n_stat_pad, q,
+                       ldq, c, ldc, lse, row_loss, logq, n, dim, pos_offset, dc, loss);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+  }, !mixed);
 }
 
 template <int D, int MODE, bool X3, bool HITS, bool HARD>
@@ -1388,49 +1391,28 @@ int launch_pass_d(dim3 grid, const PassArgs& a, hipStream_t st) {
   return TT_OK;
 }
 
-template <int MODE, bool X3 = false, bool HITS = false, bool HARD = false>
-int launch_pass(const Plan& p, const PassArgs& a, hipStream_t st) {
-  // buffer descriptors address the bf16 images with 32-bit byte offsets
-  if (p.strm_pad * p.D * 2 >= (1ll << 31))
-    return fail(TT_ERR_UNSUPPORTED, "inbatch: %lld x %d streamed batch too large", (long long)p.strm_pad, p.D);
-  dim3 grid(static_cast<unsigned>(p.stat_pad / kRowsPerWG), static_cast<unsigned>(p.split));
-  switch (p.D) {
-    case 32: return launch_pass_d<32, MODE, X3, HITS, HARD>(grid, a, st);
-    case 64: return launch_pass_d<64, MODE, X3, HITS, HARD>(grid, a, st);
-    default: return launch_pass_d<128, MODE, X3, HITS, HARD>(grid, a, st);
-  }
-}
-
 // a.stat_ids != NULL: the accidental-hit form of the pass; a.thr != NULL: the
 // hard-negative form
 template <int MODE>
-int launch_pass_any(const Plan& p, const PassArgs& a, bool x3, hipStream_t st) {
-  if (a.thr) {
-    if (a.stat_ids)
-      return x3 ? launch_pass<MODE, true, true, true>(p, a, st) : launch_pass<MODE, false, true, true>(p, a, st);
-    return x3 ? launch_pass<MODE, true, false, true>(p, a, st) : launch_pass<MODE, false, false, true>(p, a, st);
-  }
-  if (a.stat_ids) return x3 ? launch_pass<MODE, true, true>(p, a, st) : launch_pass<MODE, false, true>(p, a, st);
-  return x3 ? launch_pass<MODE, true>(p, a, st) : launch_pass<MODE>(p, a, st);
-}
-
-template <bool X3, bool HITS>
-int launch_select_d(int D, dim3 grid, const SelectArgs& a, hipStream_t st) {
-  switch (D) {
-    case 32: hipLaunchKernelGGL((hard_select_kernel<32, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((hard_select_kernel<64, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL((hard_select_kernel<128, X3, HITS>), grid, dim3(kThreads), 0, st, a); break;
-  }
-  TT_CHECK_LAUNCH();
-  return TT_OK;
+int launch_pass(const Plan& p, const PassArgs& a, bool x3, hipStream_t st) {
+  // buffer descriptors address the bf16 images with 32-bit byte offsets
+  if (p.strm_pad * p.D * 2 >= (1ll << 31))
+    return fail(TT_ERR_UNSUPPORTED, "inbatch: %lld x %d streamed batch too large", (long long)p.strm_pad, p.D);
+  const dim3 grid(static_cast<unsigned>(p.stat_pad / kRowsPerWG), static_cast<unsigned>(p.split));
+  return dispatch(p.D, [&](auto HARD, auto HITS, auto X3, auto D) -> int {
+    return launch_pass_d<D(), MODE, X3(), HITS(), HARD()>(grid, a, st);
+  }, a.thr != nullptr, a.stat_ids != nullptr, x3);
 }
 
 // The selection launch over the rows pass's prepared operands (a.stat_ids !=
 // NULL: with accidental hits at -inf).
 int launch_select(int D, int64_t stat_pad, const SelectArgs& a, bool x3, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(stat_pad / kSelRows));
-  if (a.stat_ids) return x3 ? launch_select_d<true, true>(D, grid, a, st) : launch_select_d<false, true>(D, grid, a, st);
-  return x3 ? launch_select_d<true, false>(D, grid, a, st) : launch_select_d<false, false>(D, grid, a, st);
+  return dispatch(D, [&](auto HITS, auto X3, auto d) -> int {
+    hipLaunchKernelGGL((hard_select_kernel<d(), X3(), HITS()>), grid, dim3(kThreads), 0, st, a);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+  }, a.stat_ids != nullptr, x3);
 }
 
 int pad_thr(const float* thr, int64_t n, float* dst, int64_t n_pad, hipStream_t st) {
@@ -1453,94 +1435,205 @@ int check_common(const float* q, int64_t ldq, int64_t n_rows, const float* c, in
   return TT_OK;
 }
 
-}  // namespace
-}  // namespace tt
+// ---------------------------------------------------------------------------
+// The rows / cols entries' bodies, over every mode of md.
 
-using namespace tt;
-
-namespace tt {
-namespace {
-size_t inbatch_ws_size(int64_t n_rows, int64_t n_cols, int32_t dim, bool x3, bool hits = false, bool hard = false) {
-  if (n_rows < 1 || n_cols < 1 || pick_dpad(dim) == 0) return 0;
-  const size_t a = pass_bytes(n_rows, n_cols, dim, x3, hits, hard);
-  const size_t b = pass_bytes(n_cols, n_rows, dim, x3, hits, hard);
-  return a > b ? a : b;
-}
-
-// The rows / cols entries' bodies; x3: the bf16x3 form (residual planes of
-// both operands beside the bf16 images, inbatch_pass_kernel<D, MODE, true>).
-// row_ids / col_ids (both or neither): the accidental-hit form (HITS).
-int xent_rows(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
-              int64_t n_rows, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
-              int64_t pos_offset, float* lse, float* row_loss, float* dq, void* workspace, size_t workspace_bytes,
-              tt_stream_t stream, bool hard = false, const float* thr = nullptr) {
-  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
-  if (rc) return rc;
-  TT_REQUIRE(lse && row_loss, "%s: NULL lse/row_loss", fn);
-  TT_REQUIRE(!hard || thr, "%s: NULL thr", fn);
-  TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
-             "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
-  const Plan p = make_plan(n_rows, n_cols, dim);
+// The rows side's operands, for the rows pass and for the selection: plan and
+// carve (out in p, w), the workspace check, the thresholds padded (the HARD
+// rows pass), then one prep launch per operand.
+int prep_rows(const char* fn, const Modes& md, const float* q, int64_t ldq, int64_t n_rows, const float* c,
+              int64_t ldc, int64_t n_cols, int32_t dim, const float* logq, void* workspace, size_t workspace_bytes,
+              hipStream_t st, Plan& p, PassWs& w) {
+  p = make_plan(n_rows, n_cols, dim);
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr, hard);
+  w = carve_pass(cv, p, md.x3, md.hits(), md.hard);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
-  hipStream_t st = to_stream(stream);
+  int rc;
   const PrepJob none{};
-  if (hard && (rc = pad_thr(thr, n_rows, w.thr, p.stat_pad, st))) return rc;
+  if (md.hard && md.thr && (rc = pad_thr(md.thr, n_rows, w.thr, p.stat_pad, st))) return rc;
   PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
   jq.dst_lo = w.stat_lo;
   jc.dst_lo = w.strm_lo;
-  jq.ids = row_ids, jq.ids_dst = w.stat_ids;
-  jc.ids = col_ids, jc.ids_dst = w.strm_ids;
+  jq.ids = md.row_ids, jq.ids_dst = w.stat_ids;
+  jc.ids = md.col_ids, jc.ids_dst = w.strm_ids;
   if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
-  if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
+  return prep(p.D, jc, none, dim, p.strm_pad, st);
+}
+
+int xent_rows(const char* fn, const Modes& md, const float* q, int64_t ldq, int64_t n_rows, const float* c,
+              int64_t ldc, int64_t n_cols, int32_t dim, const float* logq, int64_t pos_offset, float* lse,
+              float* row_loss, float* dq, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
+  if (rc) return rc;
+  TT_REQUIRE(lse && row_loss, "%s: NULL lse/row_loss", fn);
+  TT_REQUIRE(!md.hard || md.thr, "%s: NULL thr", fn);
+  TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
+             "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
+  hipStream_t st = to_stream(stream);
+  Plan p;
+  PassWs w;
+  if ((rc = prep_rows(fn, md, q, ldq, n_rows, c, ldc, n_cols, dim, logq, workspace, workspace_bytes, st, p, w)))
+    return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, w.part_m, w.part_l, w.part_o,
              w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids, w.thr, nullptr};
-  if ((rc = launch_pass_any<0>(p, a, x3, st))) return rc;
+  if ((rc = launch_pass<0>(p, a, md.x3, st))) return rc;
   return combine_rows(p.D, st, w.part_m, w.part_l, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, logq, n_rows, dim,
                       pos_offset, lse, row_loss, dq, nullptr);
 }
 
-int xent_cols(const char* fn, bool x3, const int32_t* row_ids, const int32_t* col_ids, const float* q, int64_t ldq,
-              int64_t n_rows, const float* lse, const float* row_loss, const float* c, int64_t ldc, int64_t n_cols,
-              int32_t dim, const float* logq, int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes,
-              tt_stream_t stream, bool hard = false, const float* thr = nullptr, bool mixed = false) {
+int xent_cols(const char* fn, const Modes& md, const float* q, int64_t ldq, int64_t n_rows, const float* lse,
+              const float* row_loss, const float* c, int64_t ldc, int64_t n_cols, int32_t dim, const float* logq,
+              int64_t pos_offset, float* dc, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
   int rc = check_common(q, ldq, n_rows, c, ldc, n_cols, dim);
   if (rc) return rc;
   TT_REQUIRE(lse && dc, "%s: NULL lse/dc", fn);
-  TT_REQUIRE(!hard || thr, "%s: NULL thr", fn);
+  TT_REQUIRE(!md.hard || md.thr, "%s: NULL thr", fn);
   // mixed: a column whose positive falls outside [0, n_rows) has none
-  TT_REQUIRE(mixed || (pos_offset >= 0 && n_cols + pos_offset <= n_rows),
+  TT_REQUIRE(md.mixed || (pos_offset >= 0 && n_cols + pos_offset <= n_rows),
              "%s: positives [pos_offset, pos_offset+n_cols) exceed n_rows", fn);
   TT_REQUIRE(pos_offset > -(1ll << 30) && pos_offset < (1ll << 30), "%s: pos_offset out of range", fn);
   const Plan p = make_plan(n_cols, n_rows, dim);  // stationary = columns, streamed = rows
   Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3, row_ids != nullptr, hard);
+  PassWs w = carve_pass(cv, p, md.x3, md.hits(), md.hard);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
   const PrepJob none{};
-  if (hard && (rc = pad_thr(thr, n_rows, w.thr, p.strm_pad, st))) return rc;
+  if (md.hard && (rc = pad_thr(md.thr, n_rows, w.thr, p.strm_pad, st))) return rc;
   PrepJob jc = prep_job(c, ldc, n_cols, dim, w.stat), jq = prep_job(q, ldq, n_rows, dim, w.strm, lse, w.bias);
-  if (hard) jc.bv = logq, jc.bias = w.stat_bias;  // -logq of the stationary columns (-inf on padded ones)
+  if (md.hard) jc.bv = logq, jc.bias = w.stat_bias;  // -logq of the stationary columns (-inf on padded ones)
   jc.dst_lo = w.stat_lo;
   jq.dst_lo = w.strm_lo;
-  jc.ids = col_ids, jc.ids_dst = w.stat_ids;
-  jq.ids = row_ids, jq.ids_dst = w.strm_ids;
+  jc.ids = md.col_ids, jc.ids_dst = w.stat_ids;
+  jq.ids = md.row_ids, jq.ids_dst = w.strm_ids;
   if ((rc = prep(p.D, jc, none, dim, p.stat_pad, st))) return rc;
   if ((rc = prep(p.D, jq, none, dim, p.strm_pad, st))) return rc;
   PassArgs a{w.stat, w.strm, w.bias, p.stat_pad, p.strm_pad, p.per_split, pos_offset, nullptr, nullptr, w.part_o,
              w.stat_lo, w.strm_lo, w.stat_ids, w.strm_ids, w.thr, w.stat_bias};
-  if ((rc = launch_pass_any<1>(p, a, x3, st))) return rc;
-  if (mixed)
-    return combine_cols_mixed(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols,
-                              dim, pos_offset, dc, n_rows);
+  if ((rc = launch_pass<1>(p, a, md.x3, st))) return rc;
   return combine_cols(p.D, st, w.part_o, p.split, p.stat_pad, q, ldq, c, ldc, lse, row_loss, logq, n_cols, dim,
-                      pos_offset, dc);
+                      pos_offset, dc, md.mixed, n_rows);
 }
+
+// ---------------------------------------------------------------------------
+// Single-device fused loss, q [n] against c [n + m]: rows and cols passes share
+// one bf16 preparation of q and c (one row-major image each, padded to 128
+// rows), the cols pass's -lse bias is written by the rows combine.
+// m = 0, the square entries: both extents padded to 128, one prep launch for
+// both matrices, 5 launches in total.  m > 0 (mixed negatives): the rows pass
+// streams c's image over round_up(n + m, 64) rows and the cols pass q's over
+// round_up(n, 64), the extents (and so the split geometry and every sum's
+// order) of the rectangular entries called at n_cols = n + m.
+struct FusedWs {
+  __bf16 *qb, *cb;
+  __bf16 *qb_lo, *cb_lo;  // x3 mode only
+  float *bias_logq, *bias_lse;
+  float *part_m, *part_l, *part_o_rows, *part_o_cols;
+  int32_t* ids;  // hits mode only: [c_pad], both passes' stationary and streamed ids
+  float* thr;    // hard mode only: [q_pad], the rows' thresholds (-inf on padded rows)
+};
+struct FusedPlan {
+  Plan rows, cols;       // rows: stationary q, streamed c; cols: the other way round
+  int64_t q_pad, c_pad;  // rows of the two images (multiples of 128)
+};
+FusedPlan fused_plan(int64_t n, int64_t m, int dim) {
+  FusedPlan p;
+  if (m == 0) {  // the square rule: one plan for both passes, streamed extent padded to 128 as well
+    Plan& s = p.rows;
+    s.D = pick_dpad(dim);
+    s.stat_pad = s.strm_pad = round_up(n > 0 ? n : 1, kRowsPerWG);  // multiple of both 128 and 64
+    s.split = pick_split(s.stat_pad, s.strm_pad);
+    s.per_split = round_up(ceil_div(s.strm_pad, s.split), kTile);
+    p.cols = s;
+  } else {
+    p.rows = make_plan(n, n + m, dim);
+    p.cols = make_plan(n + m, n, dim);
+  }
+  p.q_pad = p.rows.stat_pad;  // >= cols.strm_pad
+  p.c_pad = p.cols.stat_pad;  // >= rows.strm_pad
+  return p;
+}
+FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3, bool hits, bool hard) {
+  const int D = p.rows.D;
+  FusedWs w;
+  w.qb = cv.take<__bf16>(p.q_pad * D);
+  w.cb = cv.take<__bf16>(p.c_pad * D);
+  w.qb_lo = x3 ? cv.take<__bf16>(p.q_pad * D) : nullptr;
+  w.cb_lo = x3 ? cv.take<__bf16>(p.c_pad * D) : nullptr;
+  w.bias_logq = cv.take<float>(p.c_pad);
+  w.bias_lse = cv.take<float>(p.q_pad);
+  w.part_m = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
+  w.part_l = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
+  w.part_o_rows = cv.take<float>(int64_t(p.rows.split) * p.q_pad * D);
+  w.part_o_cols = cv.take<float>(int64_t(p.cols.split) * p.c_pad * D);
+  w.ids = hits ? cv.take<int32_t>(p.c_pad) : nullptr;  // last: the plain carve does not move
+  w.thr = hard ? cv.take<float>(p.q_pad) : nullptr;
+  return w;
+}
+
+size_t fused_ws_size(int64_t n, int64_t m, int32_t dim, bool x3 = false, bool hits = false, bool hard = false) {
+  if (n < 1 || m < 0 || pick_dpad(dim) == 0) return 0;
+  Carver cv(nullptr, 0);
+  carve_fused(cv, fused_plan(n, m, dim), x3, hits, hard);
+  return cv.used();
+}
+
+// The fused entries' body; prepped (m = 0 only): the bf16 copies and bias
+// vectors are already in the workspace (tt_inbatch_prep of q and of c on the
+// same workspace, ordered before this call).
+int fused_xent(const char* fn, const Modes& md, const float* q, int64_t ldq, int64_t n, const float* c, int64_t ldc,
+               int64_t m, int32_t dim, const float* logq, float* lse, float* row_loss, float* dq, float* dc,
+               float loss_scale, float* loss, bool prepped, void* workspace, size_t workspace_bytes,
+               tt_stream_t stream) {
+  int rc = check_common(q, ldq, n, c, ldc, n + m, dim);
+  if (rc) return rc;
+  TT_REQUIRE(lse && row_loss && dq && dc, "%s: NULL output", fn);
+  const FusedPlan p = fused_plan(n, m, dim);
+  const int D = p.rows.D;
+  Carver cv(workspace, workspace_bytes);
+  FusedWs w = carve_fused(cv, p, md.x3, md.hits(), md.hard);
+  if (!workspace || cv.used() > workspace_bytes)
+    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
+  hipStream_t st = to_stream(stream);
+  // c's job writes -logq and the ids.  The padded rows of the cols pass's bias
+  // (-lse; its [0, n) comes from the rows combine) are left at -inf by c's job
+  // in the square entries' one launch for both matrices, by q's job otherwise.
+  const bool square = m == 0;
+  PrepJob jq = prep_job(q, ldq, n, dim, w.qb, nullptr, square ? nullptr : w.bias_lse);
+  PrepJob jc = prep_job(c, ldc, n + m, dim, w.cb, logq, w.bias_logq, square ? w.bias_lse : nullptr);
+  jq.dst_lo = w.qb_lo;
+  jc.dst_lo = w.cb_lo;
+  jc.ids = md.col_ids, jc.ids_dst = w.ids;  // one padded copy: row i's id is column i's
+  if (square) {
+    if (!prepped && (rc = prep(D, jq, jc, dim, p.q_pad, st))) return rc;
+  } else {
+    const PrepJob none{};
+    if ((rc = prep(D, jq, none, dim, p.q_pad, st))) return rc;
+    if ((rc = prep(D, jc, none, dim, p.c_pad, st))) return rc;
+  }
+  if (md.hard) {  // the rows' thresholds, from the rows pass's operands
+    const SelectArgs sel{w.qb, w.cb, w.bias_logq, n, p.rows.strm_pad, 0, w.qb_lo, w.cb_lo, w.ids, w.ids,
+                         clamp_k(md.hard_k), md.thr_out, w.thr};
+    if ((rc = launch_select(D, p.q_pad, sel, md.x3, st))) return rc;
+  }
+  PassArgs ar{w.qb, w.cb, w.bias_logq, p.q_pad, p.rows.strm_pad, p.rows.per_split, 0, w.part_m, w.part_l,
+              w.part_o_rows, w.qb_lo, w.cb_lo, w.ids, w.ids, w.thr, nullptr};
+  if ((rc = launch_pass<0>(p.rows, ar, md.x3, st))) return rc;
+  if ((rc = combine_rows(D, st, w.part_m, w.part_l, w.part_o_rows, p.rows.split, p.q_pad, q, ldq, c, ldc, logq, n,
+                         dim, 0, lse, row_loss, dq, w.bias_lse)))
+    return rc;
+  PassArgs ac{w.cb, w.qb, w.bias_lse, p.c_pad, p.cols.strm_pad, p.cols.per_split, 0, nullptr, nullptr,
+              w.part_o_cols, w.cb_lo, w.qb_lo, w.ids, w.ids, w.thr, w.bias_logq};
+  if ((rc = launch_pass<1>(p.cols, ac, md.x3, st))) return rc;
+  return combine_cols(D, st, w.part_o_cols, p.cols.split, p.c_pad, q, ldq, c, ldc, lse, row_loss, logq, n + m, dim, 0,
+                      dc, !square, n, loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
+}
+
 }  // namespace
 }  // namespace tt
+
+using namespace tt;
 
 extern "C" size_t tt_inbatch_workspace_size(int64_t n_rows, int64_t n_cols, int32_t dim) {
   return inbatch_ws_size(n_rows, n_cols, dim, false);
@@ -1551,8 +1644,8 @@ extern "C" int tt_inbatch_xent_rows(const float* q, int64_t ldq, int64_t n_rows,
                                     float* lse, float* row_loss, float* dq, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_rows("tt_inbatch_xent_rows", false, nullptr, nullptr, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
-                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
+  return xent_rows("tt_inbatch_xent_rows", Modes{}, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset, lse,
+                   row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1560,8 +1653,8 @@ extern "C" int tt_inbatch_xent_cols(const float* q, int64_t ldq, int64_t n_rows,
                                     const float* logq, int64_t pos_offset, float* dc, void* workspace,
                                     size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_cols("tt_inbatch_xent_cols", false, nullptr, nullptr, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols,
-                   dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
+  return xent_cols("tt_inbatch_xent_cols", Modes{}, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
+                   pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // The same two entries with fp32-faithful products (X3, as
@@ -1577,8 +1670,8 @@ extern "C" int tt_inbatch_xent_rows_x3(const float* q, int64_t ldq, int64_t n_ro
                                        float* lse, float* row_loss, float* dq, void* workspace,
                                        size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_rows("tt_inbatch_xent_rows_x3", true, nullptr, nullptr, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
-                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
+  return xent_rows("tt_inbatch_xent_rows_x3", Modes{true}, q, ldq, n_rows, c, ldc, n_cols, dim, logq, pos_offset,
+                   lse, row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols_x3(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1586,8 +1679,8 @@ extern "C" int tt_inbatch_xent_cols_x3(const float* q, int64_t ldq, int64_t n_ro
                                        int32_t dim, const float* logq, int64_t pos_offset, float* dc,
                                        void* workspace, size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
-  return xent_cols("tt_inbatch_xent_cols_x3", true, nullptr, nullptr, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols,
-                   dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
+  return xent_cols("tt_inbatch_xent_cols_x3", Modes{true}, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
+                   pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // Accidental-hit removal (HITS): the same entries over S' with the pairs
@@ -1603,8 +1696,8 @@ extern "C" int tt_inbatch_xent_rows_hits(const float* q, int64_t ldq, int64_t n_
                                          tt_stream_t stream) {
   clear_error();
   TT_REQUIRE(row_ids && col_ids, "tt_inbatch_xent_rows_hits: NULL row_ids/col_ids");
-  return xent_rows("tt_inbatch_xent_rows_hits", x3 != 0, row_ids, col_ids, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
-                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
+  return xent_rows("tt_inbatch_xent_rows_hits", Modes{x3 != 0, row_ids, col_ids}, q, ldq, n_rows, c, ldc, n_cols,
+                   dim, logq, pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols_hits(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1614,154 +1707,56 @@ extern "C" int tt_inbatch_xent_cols_hits(const float* q, int64_t ldq, int64_t n_
                                          size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
   TT_REQUIRE(row_ids && col_ids, "tt_inbatch_xent_cols_hits: NULL row_ids/col_ids");
-  return xent_cols("tt_inbatch_xent_cols_hits", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
-                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
+  return xent_cols("tt_inbatch_xent_cols_hits", Modes{x3 != 0, row_ids, col_ids}, q, ldq, n_rows, lse, row_loss, c,
+                   ldc, n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
-// Single-device fused loss: rows and cols passes share one bf16 preparation of
-// q and c (one row-major image each), the cols pass's -lse bias is
-// written by the rows combine.  5 launches in total.
-namespace tt {
-namespace {
-struct FusedWs {
-  __bf16 *qb, *cb;
-  __bf16 *qb_lo, *cb_lo;  // x3 mode only
-  float *bias_logq, *bias_lse;
-  float *part_m, *part_l, *part_o_rows, *part_o_cols;
-  int32_t* ids;  // hits mode only: [n_pad], both passes' stationary and streamed ids
-  float* thr;    // hard mode only: [n_pad], the rows' thresholds (-inf on padded rows)
-};
-struct FusedPlan {
-  int D;
-  int64_t n_pad;
-  int split;
-  int64_t per_split;
-};
-FusedPlan fused_plan(int64_t n, int dim) {
-  FusedPlan p;
-  p.D = pick_dpad(dim);
-  p.n_pad = round_up(n > 0 ? n : 1, kRowsPerWG);  // multiple of both 128 and 64
-  p.split = pick_split(p.n_pad, p.n_pad);
-  p.per_split = round_up(ceil_div(p.n_pad, p.split), kTile);
-  return p;
-}
-FusedWs carve_fused(Carver& cv, const FusedPlan& p, bool x3 = false, bool hits = false, bool hard = false) {
-  FusedWs w;
-  w.qb = cv.take<__bf16>(p.n_pad * p.D);
-  w.cb = cv.take<__bf16>(p.n_pad * p.D);
-  w.qb_lo = x3 ? cv.take<__bf16>(p.n_pad * p.D) : nullptr;
-  w.cb_lo = x3 ? cv.take<__bf16>(p.n_pad * p.D) : nullptr;
-  w.bias_logq = cv.take<float>(p.n_pad);
-  w.bias_lse = cv.take<float>(p.n_pad);
-  w.part_m = cv.take<float>(int64_t(p.split) * p.n_pad);
-  w.part_l = cv.take<float>(int64_t(p.split) * p.n_pad);
-  w.part_o_rows = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
-  w.part_o_cols = cv.take<float>(int64_t(p.split) * p.n_pad * p.D);
-  w.ids = hits ? cv.take<int32_t>(p.n_pad) : nullptr;  // last: the plain carve does not move
-  w.thr = hard ? cv.take<float>(p.n_pad) : nullptr;
-  return w;
-}
-}  // namespace
-}  // namespace tt
-
-extern "C" size_t tt_inbatch_fused_workspace_size(int64_t n, int32_t dim) {
-  if (n < 1 || pick_dpad(dim) == 0) return 0;
-  Carver cv(nullptr, 0);
-  carve_fused(cv, fused_plan(n, dim));
-  return cv.used();
-}
-
-namespace tt {
-namespace {
-// The fused entry's body; prepped: the bf16 copies and bias vectors are
-// already in the workspace (tt_inbatch_prep of q and of c on the same
-// workspace, ordered before this call).
-int softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n, int32_t dim, const float* logq,
-                 float* lse, float* row_loss, float* dq, float* dc, void* workspace, size_t workspace_bytes,
-                 tt_stream_t stream, bool prepped, float loss_scale = 1.0f, float* loss = nullptr, bool x3 = false,
-                 const int32_t* ids = nullptr, int64_t hard_k = 0, float* thr = nullptr) {
-  int rc = check_common(q, ldq, n, c, ldc, n, dim);
-  if (rc) return rc;
-  TT_REQUIRE(lse && row_loss && dq && dc, "tt_inbatch_softmax_xent: NULL output");
-  const FusedPlan p = fused_plan(n, dim);
-  Carver cv(workspace, workspace_bytes);
-  FusedWs w = carve_fused(cv, p, x3, ids != nullptr, hard_k > 0);
-  if (!workspace || cv.used() > workspace_bytes)
-    return fail(TT_ERR_WORKSPACE, "tt_inbatch_softmax_xent: workspace %zu < required %zu", workspace_bytes,
-                cv.used());
-  hipStream_t st = to_stream(stream);
-  // one prep launch for both matrices; c's job also writes both bias vectors
-  PrepJob jq = prep_job(q, ldq, n, dim, w.qb), jc = prep_job(c, ldc, n, dim, w.cb, logq, w.bias_logq, w.bias_lse);
-  jq.dst_lo = w.qb_lo;
-  jc.dst_lo = w.cb_lo;
-  jc.ids = ids, jc.ids_dst = w.ids;  // one padded copy serves rows and columns
-  if (!prepped && (rc = prep(p.D, jq, jc, dim, p.n_pad, st))) return rc;
-  const Plan pl{p.D, p.n_pad, p.n_pad, p.split, p.per_split};
-  if (hard_k > 0) {  // the rows' thresholds, from the rows pass's operands
-    const SelectArgs sel{w.qb, w.cb, w.bias_logq, n, p.n_pad, 0, w.qb_lo, w.cb_lo, w.ids, w.ids, clamp_k(hard_k),
-                         thr, w.thr};
-    if ((rc = launch_select(p.D, p.n_pad, sel, x3, st))) return rc;
-  }
-  PassArgs ar{w.qb, w.cb, w.bias_logq, p.n_pad, p.n_pad, p.per_split, 0, w.part_m, w.part_l, w.part_o_rows,
-              w.qb_lo, w.cb_lo, w.ids, w.ids, w.thr, nullptr};
-  if ((rc = launch_pass_any<0>(pl, ar, x3, st))) return rc;
-  if ((rc = combine_rows(p.D, st, w.part_m, w.part_l, w.part_o_rows, p.split, p.n_pad, q, ldq, c, ldc, logq, n, dim,
-                         0, lse, row_loss, dq, w.bias_lse)))
-    return rc;
-  PassArgs ac{w.cb, w.qb, w.bias_lse, p.n_pad, p.n_pad, p.per_split, 0, nullptr, nullptr, w.part_o_cols,
-              w.cb_lo, w.qb_lo, w.ids, w.ids, w.thr, w.bias_logq};
-  if ((rc = launch_pass_any<1>(pl, ac, x3, st))) return rc;
-  return combine_cols(p.D, st, w.part_o_cols, p.split, p.n_pad, q, ldq, c, ldc, lse, row_loss, logq, n, dim, 0, dc,
-                      loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
-}
-}  // namespace
-}  // namespace tt
+// The single-device fused loss (fused_xent at m = 0).
+extern "C" size_t tt_inbatch_fused_workspace_size(int64_t n, int32_t dim) { return fused_ws_size(n, 0, dim); }
 
 extern "C" int tt_inbatch_softmax_xent(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
                                        int32_t dim, const float* logq, float* lse, float* row_loss, float* dq,
                                        float* dc, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false);
+  return fused_xent("tt_inbatch_softmax_xent", Modes{}, q, ldq, n, c, ldc, 0, dim, logq, lse, row_loss, dq, dc, 1.0f,
+                    nullptr, false, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_softmax_xent_prepped(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
                                                int32_t dim, const float* logq, float* lse, float* row_loss,
                                                float* dq, float* dc, void* workspace, size_t workspace_bytes,
                                                tt_stream_t stream) {
-  using namespace tt;
   clear_error();
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, true);
+  return fused_xent("tt_inbatch_softmax_xent_prepped", Modes{}, q, ldq, n, c, ldc, 0, dim, logq, lse, row_loss, dq,
+                    dc, 1.0f, nullptr, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_softmax_xent_loss(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
                                             int32_t dim, const float* logq, float* lse, float* row_loss, float* dq,
                                             float* dc, float loss_scale, float* loss, int32_t prepped,
                                             void* workspace, size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
   TT_REQUIRE(loss, "tt_inbatch_softmax_xent_loss: NULL loss");
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream,
-                      prepped != 0, loss_scale, loss);
+  return fused_xent("tt_inbatch_softmax_xent_loss", Modes{}, q, ldq, n, c, ldc, 0, dim, logq, lse, row_loss, dq, dc,
+                    loss_scale, loss, prepped != 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_prep(const float* x, int64_t ldx, int64_t n, int32_t dim, int32_t operand,
                                const float* logq, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
   int rc = check_common(x, ldx, n, x, ldx, n, dim);
   if (rc) return rc;
   TT_REQUIRE(operand == 0 || operand == 1, "tt_inbatch_prep: operand %d is not 0 (q) or 1 (c)", operand);
-  const FusedPlan p = fused_plan(n, dim);
+  const FusedPlan p = fused_plan(n, 0, dim);
   Carver cv(workspace, workspace_bytes);
-  FusedWs w = carve_fused(cv, p);
+  FusedWs w = carve_fused(cv, p, false, false, false);
   if (!workspace || cv.used() > workspace_bytes)
     return fail(TT_ERR_WORKSPACE, "tt_inbatch_prep: workspace %zu < required %zu", workspace_bytes, cv.used());
   const PrepJob none{};
-  return prep(p.D, operand == 0 ? prep_job(x, ldx, n, dim, w.qb) : prep_job(x, ldx, n, dim, w.cb, logq, w.bias_logq,
-                                                                              w.bias_lse),
-              none, dim, p.n_pad, to_stream(stream));
+  return prep(p.rows.D, operand == 0 ? prep_job(x, ldx, n, dim, w.qb) : prep_job(x, ldx, n, dim, w.cb, logq,
+                                                                                   w.bias_logq, w.bias_lse),
+              none, dim, p.q_pad, to_stream(stream));
 }
 
 // Opt-in fp32-faithful products (X3): the fused loss with S = Q.C^T and the
@@ -1771,29 +1766,22 @@ extern "C" int tt_inbatch_prep(const float* x, int64_t ldx, int64_t n, int32_t d
 // magnitudes (|S| ~ 100) keep their fp32 values.  Three MFMAs where the
 // default issues one, one workgroup per CU: ~3x the passes' time.
 extern "C" size_t tt_inbatch_fused_x3_workspace_size(int64_t n, int32_t dim) {
-  if (n < 1 || pick_dpad(dim) == 0) return 0;
-  Carver cv(nullptr, 0);
-  carve_fused(cv, fused_plan(n, dim), true);
-  return cv.used();
+  return fused_ws_size(n, 0, dim, true);
 }
 
 extern "C" int tt_inbatch_softmax_xent_x3(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
                                           int32_t dim, const float* logq, float* lse, float* row_loss, float* dq,
                                           float* dc, float loss_scale, float* loss, void* workspace,
                                           size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
-                      loss_scale, loss, true);
+  return fused_xent("tt_inbatch_softmax_xent_x3", Modes{true}, q, ldq, n, c, ldc, 0, dim, logq, lse, row_loss, dq,
+                    dc, loss_scale, loss, false, workspace, workspace_bytes, stream);
 }
 
 // Accidental-hit removal (HITS), single device: ids [n] are both the rows'
 // and the columns' candidate ids; loss may be NULL; x3 != 0: the bf16x3 form.
 extern "C" size_t tt_inbatch_fused_hits_workspace_size(int64_t n, int32_t dim, int32_t x3) {
-  if (n < 1 || pick_dpad(dim) == 0) return 0;
-  Carver cv(nullptr, 0);
-  carve_fused(cv, fused_plan(n, dim), x3 != 0, true);
-  return cv.used();
+  return fused_ws_size(n, 0, dim, x3 != 0, true);
 }
 
 extern "C" int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
@@ -1801,11 +1789,10 @@ extern "C" int tt_inbatch_softmax_xent_hits(const float* q, int64_t ldq, const f
                                             float* lse, float* row_loss, float* dq, float* dc, float loss_scale,
                                             float* loss, void* workspace, size_t workspace_bytes,
                                             tt_stream_t stream) {
-  using namespace tt;
   clear_error();
   TT_REQUIRE(ids, "tt_inbatch_softmax_xent_hits: NULL ids");
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
-                      loss_scale, loss, x3 != 0, ids);
+  return fused_xent("tt_inbatch_softmax_xent_hits", Modes{x3 != 0, ids, ids}, q, ldq, n, c, ldc, 0, dim, logq, lse,
+                    row_loss, dq, dc, loss_scale, loss, false, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1829,23 +1816,15 @@ extern "C" int tt_inbatch_hard_threshold(const float* q, int64_t ldq, int64_t n_
   TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "%s: row_ids and col_ids go together", fn);
   TT_REQUIRE(pos_offset >= 0 && n_rows + pos_offset <= n_cols,
              "%s: positives [pos_offset, pos_offset+n_rows) exceed n_cols", fn);
-  const Plan p = make_plan(n_rows, n_cols, dim);
-  Carver cv(workspace, workspace_bytes);
-  PassWs w = carve_pass(cv, p, x3 != 0, row_ids != nullptr, true);
-  if (!workspace || cv.used() > workspace_bytes)
-    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
   hipStream_t st = to_stream(stream);
-  const PrepJob none{};
-  PrepJob jq = prep_job(q, ldq, n_rows, dim, w.stat), jc = prep_job(c, ldc, n_cols, dim, w.strm, logq, w.bias);
-  jq.dst_lo = w.stat_lo;
-  jc.dst_lo = w.strm_lo;
-  jq.ids = row_ids, jq.ids_dst = w.stat_ids;
-  jc.ids = col_ids, jc.ids_dst = w.strm_ids;
-  if ((rc = prep(p.D, jq, none, dim, p.stat_pad, st))) return rc;
-  if ((rc = prep(p.D, jc, none, dim, p.strm_pad, st))) return rc;
+  const Modes md{x3 != 0, row_ids, col_ids, true};  // the HARD rows pass's carve; no thresholds to pad yet
+  Plan p;
+  PassWs w;
+  if ((rc = prep_rows(fn, md, q, ldq, n_rows, c, ldc, n_cols, dim, logq, workspace, workspace_bytes, st, p, w)))
+    return rc;
   const SelectArgs sel{w.stat, w.strm, w.bias, n_rows, p.strm_pad, pos_offset, w.stat_lo, w.strm_lo, w.stat_ids,
                        w.strm_ids, clamp_k(k), thr, nullptr};
-  return launch_select(p.D, p.stat_pad, sel, x3 != 0, st);
+  return launch_select(p.D, p.stat_pad, sel, md.x3, st);
 }
 
 extern "C" int tt_inbatch_xent_rows_hard(const float* q, int64_t ldq, int64_t n_rows, const float* c, int64_t ldc,
@@ -1855,8 +1834,8 @@ extern "C" int tt_inbatch_xent_rows_hard(const float* q, int64_t ldq, int64_t n_
                                          size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
   TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "tt_inbatch_xent_rows_hard: row_ids and col_ids go together");
-  return xent_rows("tt_inbatch_xent_rows_hard", x3 != 0, row_ids, col_ids, q, ldq, n_rows, c, ldc, n_cols, dim, logq,
-                   pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream, true, thr);
+  return xent_rows("tt_inbatch_xent_rows_hard", Modes{x3 != 0, row_ids, col_ids, true, thr}, q, ldq, n_rows, c, ldc,
+                   n_cols, dim, logq, pos_offset, lse, row_loss, dq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tt_inbatch_xent_cols_hard(const float* q, int64_t ldq, int64_t n_rows, const float* lse,
@@ -1866,15 +1845,12 @@ extern "C" int tt_inbatch_xent_cols_hard(const float* q, int64_t ldq, int64_t n_
                                          void* workspace, size_t workspace_bytes, tt_stream_t stream) {
   clear_error();
   TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr), "tt_inbatch_xent_cols_hard: row_ids and col_ids go together");
-  return xent_cols("tt_inbatch_xent_cols_hard", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
-                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream, true, thr);
+  return xent_cols("tt_inbatch_xent_cols_hard", Modes{x3 != 0, row_ids, col_ids, true, thr}, q, ldq, n_rows, lse,
+                   row_loss, c, ldc, n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t tt_inbatch_fused_hard_workspace_size(int64_t n, int32_t dim, int32_t x3) {
-  if (n < 1 || pick_dpad(dim) == 0) return 0;
-  Carver cv(nullptr, 0);
-  carve_fused(cv, fused_plan(n, dim), x3 != 0, true, true);
-  return cv.used();
+  return fused_ws_size(n, 0, dim, x3 != 0, true, true);
 }
 
 extern "C" int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const float* c, int64_t ldc, int64_t n,
@@ -1882,12 +1858,12 @@ extern "C" int tt_inbatch_softmax_xent_hard(const float* q, int64_t ldq, const f
                                             int64_t k, float* lse, float* row_loss, float* dq, float* dc,
                                             float* thr, float loss_scale, float* loss, void* workspace,
                                             size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
   TT_REQUIRE(k >= 1, "tt_inbatch_softmax_xent_hard: k must be >= 1");
   TT_REQUIRE(thr, "tt_inbatch_softmax_xent_hard: NULL thr");
-  return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
-                      loss_scale, loss, x3 != 0, ids, k, thr);
+  return fused_xent("tt_inbatch_softmax_xent_hard", Modes{x3 != 0, ids, ids, true, nullptr, k, thr}, q, ldq, n, c,
+                    ldc, 0, dim, logq, lse, row_loss, dq, dc, loss_scale, loss, false, workspace, workspace_bytes,
+                    stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1907,67 +1883,19 @@ extern "C" int tt_inbatch_xent_cols_mixed(const float* q, int64_t ldq, int64_t n
   clear_error();
   TT_REQUIRE((row_ids == nullptr) == (col_ids == nullptr),
              "tt_inbatch_xent_cols_mixed: row_ids and col_ids go together");
-  return xent_cols("tt_inbatch_xent_cols_mixed", x3 != 0, row_ids, col_ids, q, ldq, n_rows, lse, row_loss, c, ldc,
-                   n_cols, dim, logq, pos_offset, dc, workspace, workspace_bytes, stream, thr != nullptr, thr, true);
+  Modes md{x3 != 0, row_ids, col_ids, thr != nullptr, thr};
+  md.mixed = true;
+  return xent_cols("tt_inbatch_xent_cols_mixed", md, q, ldq, n_rows, lse, row_loss, c, ldc, n_cols, dim, logq,
+                   pos_offset, dc, workspace, workspace_bytes, stream);
 }
 
-// Single device: q [n] against c [n + m].  One bf16 preparation of each
-// operand, padded to 128 rows, serves both passes: the rows pass streams c's
-// image over round_up(n + m, 64) rows and the cols pass q's over
-// round_up(n, 64), the extents (and so the split geometry and every sum's
-// order) of the rectangular entries called at n_cols = n + m.  m = 0 is the
-// square fused entry itself.
-namespace tt {
-namespace {
-struct MixedWs {
-  __bf16 *qb, *cb;
-  __bf16 *qb_lo, *cb_lo;
-  float *bias_logq, *bias_lse;
-  float *part_m, *part_l, *part_o_rows, *part_o_cols;
-  int32_t* ids;
-  float* thr;
-};
-struct MixedPlan {
-  Plan rows, cols;        // rows: stationary q, streamed c; cols: the other way round
-  int64_t q_pad, c_pad;   // rows of the two images (multiples of 128)
-};
-MixedPlan mixed_plan(int64_t n, int64_t m, int dim) {
-  MixedPlan p;
-  p.rows = make_plan(n, n + m, dim);
-  p.cols = make_plan(n + m, n, dim);
-  p.q_pad = p.rows.stat_pad;  // >= cols.strm_pad
-  p.c_pad = p.cols.stat_pad;  // >= rows.strm_pad
-  return p;
-}
-MixedWs carve_mixed(Carver& cv, const MixedPlan& p, bool x3, bool hits, bool hard) {
-  const int D = p.rows.D;
-  MixedWs w;
-  w.qb = cv.take<__bf16>(p.q_pad * D);
-  w.cb = cv.take<__bf16>(p.c_pad * D);
-  w.qb_lo = x3 ? cv.take<__bf16>(p.q_pad * D) : nullptr;
-  w.cb_lo = x3 ? cv.take<__bf16>(p.c_pad * D) : nullptr;
-  w.bias_logq = cv.take<float>(p.c_pad);
-  w.bias_lse = cv.take<float>(p.q_pad);
-  w.part_m = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
-  w.part_l = cv.take<float>(int64_t(p.rows.split) * p.q_pad);
-  w.part_o_rows = cv.take<float>(int64_t(p.rows.split) * p.q_pad * D);
-  w.part_o_cols = cv.take<float>(int64_t(p.cols.split) * p.c_pad * D);
-  w.ids = hits ? cv.take<int32_t>(p.c_pad) : nullptr;
-  w.thr = hard ? cv.take<float>(p.q_pad) : nullptr;
-  return w;
-}
-}  // namespace
-}  // namespace tt
-
+// Single device: q [n] against c [n + m] (fused_xent).  m = 0 is the square
+// fused entry itself, and the workspace holds that one's at every m.
 extern "C" size_t tt_inbatch_fused_mixed_workspace_size(int64_t n, int64_t m, int32_t dim, int32_t x3) {
-  if (n < 1 || m < 0 || pick_dpad(dim) == 0) return 0;
-  Carver cv(nullptr, 0);
-  carve_fused(cv, fused_plan(n, dim), x3 != 0, true, true);  // m = 0: the square entry's
-  const size_t sq = cv.used();
-  if (m == 0) return sq;
-  Carver cm(nullptr, 0);
-  carve_mixed(cm, mixed_plan(n, m, dim), x3 != 0, true, true);
-  return cm.used() > sq ? cm.used() : sq;
+  const size_t a = fused_ws_size(n, m, dim, x3 != 0, true, true);
+  if (a == 0 || m == 0) return a;
+  const size_t sq = fused_ws_size(n, 0, dim, x3 != 0, true, true);
+  return a > sq ? a : sq;
 }
 
 extern "C" int tt_inbatch_softmax_xent_mixed(const float* q, int64_t ldq, int64_t n, const float* c, int64_t ldc,
@@ -1975,50 +1903,11 @@ extern "C" int tt_inbatch_softmax_xent_mixed(const float* q, int64_t ldq, int64_
                                              int32_t x3, int64_t k, float* lse, float* row_loss, float* dq,
                                              float* dc, float* thr, float loss_scale, float* loss, void* workspace,
                                              size_t workspace_bytes, tt_stream_t stream) {
-  using namespace tt;
   clear_error();
   const char* fn = "tt_inbatch_softmax_xent_mixed";
   TT_REQUIRE(m >= 0, "%s: m must be >= 0", fn);
   TT_REQUIRE(k >= 0, "%s: k must be >= 0 (0: no mining)", fn);
   TT_REQUIRE(k == 0 || thr, "%s: NULL thr", fn);
-  if (m == 0)
-    return softmax_xent(q, ldq, c, ldc, n, dim, logq, lse, row_loss, dq, dc, workspace, workspace_bytes, stream, false,
-                        loss_scale, loss, x3 != 0, ids, k, thr);
-  int rc = check_common(q, ldq, n, c, ldc, n + m, dim);
-  if (rc) return rc;
-  TT_REQUIRE(lse && row_loss && dq && dc, "%s: NULL output", fn);
-  const bool X3 = x3 != 0, hard = k > 0;
-  const MixedPlan p = mixed_plan(n, m, dim);
-  const int D = p.rows.D;
-  Carver cv(workspace, workspace_bytes);
-  MixedWs w = carve_mixed(cv, p, X3, ids != nullptr, hard);
-  if (!workspace || cv.used() > workspace_bytes)
-    return fail(TT_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes, cv.used());
-  hipStream_t st = to_stream(stream);
-  const PrepJob none{};
-  // q's job leaves -inf on the padded rows of the cols pass's bias (-lse;
-  // its [0, n) comes from the rows combine), c's job writes -logq and the ids
-  PrepJob jq = prep_job(q, ldq, n, dim, w.qb, nullptr, w.bias_lse);
-  PrepJob jc = prep_job(c, ldc, n + m, dim, w.cb, logq, w.bias_logq);
-  jq.dst_lo = w.qb_lo;
-  jc.dst_lo = w.cb_lo;
-  jc.ids = ids, jc.ids_dst = w.ids;  // one padded copy: row i's id is column i's
-  if ((rc = prep(D, jq, none, dim, p.q_pad, st))) return rc;
-  if ((rc = prep(D, jc, none, dim, p.c_pad, st))) return rc;
-  if (hard) {
-    const SelectArgs sel{w.qb, w.cb, w.bias_logq, n, p.rows.strm_pad, 0, w.qb_lo, w.cb_lo, w.ids, w.ids, clamp_k(k),
-                         thr, w.thr};
-    if ((rc = launch_select(D, p.q_pad, sel, X3, st))) return rc;
-  }
-  PassArgs ar{w.qb, w.cb, w.bias_logq, p.q_pad, p.rows.strm_pad, p.rows.per_split, 0, w.part_m, w.part_l,
-              w.part_o_rows, w.qb_lo, w.cb_lo, w.ids, w.ids, w.thr, nullptr};
-  if ((rc = launch_pass_any<0>(p.rows, ar, X3, st))) return rc;
-  if ((rc = combine_rows(D, st, w.part_m, w.part_l, w.part_o_rows, p.rows.split, p.q_pad, q, ldq, c, ldc, logq, n,
-                         dim, 0, lse, row_loss, dq, w.bias_lse)))
-    return rc;
-  PassArgs ac{w.cb, w.qb, w.bias_lse, p.c_pad, p.cols.strm_pad, p.cols.per_split, 0, nullptr, nullptr,
-              w.part_o_cols, w.cb_lo, w.qb_lo, w.ids, w.ids, w.thr, w.bias_logq};
-  if ((rc = launch_pass_any<1>(p.cols, ac, X3, st))) return rc;
-  return combine_cols_mixed(D, st, w.part_o_cols, p.cols.split, p.c_pad, q, ldq, c, ldc, lse, row_loss, logq, n + m,
-                            dim, 0, dc, n, loss ? LossSum{row_loss, n, loss_scale, loss} : LossSum{});
+  return fused_xent(fn, Modes{x3 != 0, ids, ids, k > 0, nullptr, k, thr}, q, ldq, n, c, ldc, m, dim, logq, lse,
+                    row_loss, dq, dc, loss_scale, loss, false, workspace, workspace_bytes, stream);
 }

@@ -837,9 +837,42 @@ def _hard_k(k) -> int:
     return k
 
 
-def _hard_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool) -> torch.Tensor:
-    return Workspace.get(L.tt_inbatch_hard_workspace_size(R, C, E, int(x3)), device,
-                         "inbatch_hard_x3" if x3 else "inbatch_hard")
+def _inbatch_operands(q: torch.Tensor, c: torch.Tensor, shapes: Optional[str] = "dim"):
+    """The in-batch entries' operand checks: (ldq, ldc, R, C, E) of q [R, E]
+    and c [C, E].  shapes: the agreement asked of them — "dim" (one embedding
+    size), "square" (C = R), "mixed" (C >= R) or None (left to the library)."""
+    _req(q, "q", torch.float32, 2)
+    _req(c, "c", torch.float32, 2)
+    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
+    R, E = q.shape
+    C = c.shape[0]
+    if shapes == "dim" and c.shape[1] != E:
+        raise ValueError("q and c must share the embedding size")
+    if shapes == "square" and tuple(c.shape) != (R, E):
+        raise ValueError("q and c must both be [B, E]")
+    if shapes == "mixed" and (c.shape[1] != E or C < R):
+        raise ValueError(f"c must be [B + M, E] with M >= 0 for q [B, E], got {tuple(c.shape)} for {tuple(q.shape)}")
+    return ldq, ldc, R, C, E
+
+
+def _inbatch_variant(L, R: int, C: int, E: int, device: torch.device, x3: bool, hits, hard: bool = False,
+                     mixed: bool = False):
+    """What the options change in a rows / cols / threshold call: (the entry's
+    suffix, its workspace, the arguments (row_ids, col_ids, x3) after
+    pos_offset — none for the plain and _x3 entries, which have no such
+    parameters).  hits: _ids_pair's result."""
+    kind = "mixed" if mixed else "hard" if hard else "hits" if hits is not None else None
+    if kind is None:
+        size = (L.tt_inbatch_x3_workspace_size if x3 else L.tt_inbatch_workspace_size)(R, C, E)
+        suffix, tag, mid = "_x3" if x3 else "", "inbatch", ()
+    else:
+        size = getattr(L, f"tt_inbatch_{kind}_workspace_size")(R, C, E, int(x3))
+        suffix, tag, mid = "_" + kind, "inbatch_" + kind, (*(hits or (None, None)), int(x3))
+    return suffix, Workspace.get(size, device, tag + ("_x3" if x3 else "")), mid
+
+
+def _empty(device: torch.device, *shape: int) -> torch.Tensor:
+    return torch.empty(shape, dtype=torch.float32, device=device)
 
 
 def inbatch_hard_threshold(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], k: int,
@@ -854,20 +887,12 @@ def inbatch_hard_threshold(q: torch.Tensor, c: torch.Tensor, logq: Optional[torc
     all kept (include/tt.h)."""
     k = _hard_k(k)
     hits = _ids_pair(row_ids, col_ids, q, c)
-    _req(q, "q", torch.float32, 2)
-    _req(c, "c", torch.float32, 2)
-    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
-    R, E = q.shape
-    C = c.shape[0]
-    if c.shape[1] != E:
-        raise ValueError("q and c must share the embedding size")
+    ldq, ldc, R, C, E = _inbatch_operands(q, c)
     L = lib()
-    ws = _hard_workspace(L, R, C, E, q.device, x3)
-    thr = torch.empty(R, dtype=torch.float32, device=q.device)
-    rid, cid = hits if hits is not None else (None, None)
+    _, ws, mid = _inbatch_variant(L, R, C, E, q.device, x3, hits, hard=True)
+    thr = _empty(q.device, R)
     check(L.tt_inbatch_hard_threshold(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
-                                      pos_offset, rid, cid, int(x3), k, thr.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      _stream()))
+                                      pos_offset, *mid, k, thr.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return thr
 
 
@@ -884,48 +909,18 @@ def inbatch_rows(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
     and x3): hard-negative mining (tt_inbatch_xent_rows_hard) — a negative
     with S' below its row's threshold has weight 0."""
     hits = _ids_pair(row_ids, col_ids, q, c)
-    _req(q, "q", torch.float32, 2)
-    _req(c, "c", torch.float32, 2)
-    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
-    R, E = q.shape
-    C = c.shape[0]
-    if c.shape[1] != E:
-        raise ValueError("q and c must share the embedding size")
+    ldq, ldc, R, C, E = _inbatch_operands(q, c)
     L = lib()
-    lse = torch.empty(R, dtype=torch.float32, device=q.device)
-    row_loss = torch.empty(R, dtype=torch.float32, device=q.device)
-    dq = torch.empty(R, E, dtype=torch.float32, device=q.device) if want_dq else None
+    lse, row_loss = _empty(q.device, R), _empty(q.device, R)
+    dq = _empty(q.device, R, E) if want_dq else None
+    suffix, ws, mid = _inbatch_variant(L, R, C, E, q.device, x3, hits, hard=thr is not None)
+    head = (q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C), pos_offset)
     if thr is not None:
-        rid, cid = hits if hits is not None else (None, None)
-        ws = _hard_workspace(L, R, C, E, q.device, x3)
-        check(L.tt_inbatch_xent_rows_hard(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
-                                          pos_offset, rid, cid, int(x3), _opt_ptr(thr, "thr", R), lse.data_ptr(),
-                                          row_loss.data_ptr(), dq.data_ptr() if dq is not None else None,
-                                          ws.data_ptr(), ws.numel(), _stream()))
-        return lse, row_loss, dq
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
-    if hits is not None:
-        rid, cid = hits
-        check(L.tt_inbatch_xent_rows_hits(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C),
-                                          pos_offset, rid, cid, int(x3), lse.data_ptr(), row_loss.data_ptr(),
-                                          dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(),
-                                          _stream()))
-        return lse, row_loss, dq
-    fn = L.tt_inbatch_xent_rows_x3 if x3 else L.tt_inbatch_xent_rows
-    check(fn(q.data_ptr(), ldq, R, c.data_ptr(), ldc, C, E, _opt_ptr(logq, "logq", C), pos_offset, lse.data_ptr(),
-             row_loss.data_ptr(), dq.data_ptr() if dq is not None else None, ws.data_ptr(), ws.numel(), _stream()))
+        mid += (_opt_ptr(thr, "thr", R),)
+    check(getattr(L, "tt_inbatch_xent_rows" + suffix)(
+        *head, *mid, lse.data_ptr(), row_loss.data_ptr(), dq.data_ptr() if dq is not None else None, ws.data_ptr(),
+        ws.numel(), _stream()))
     return lse, row_loss, dq
-
-
-def _inbatch_workspace(L, R: int, C: int, E: int, device: torch.device, x3: bool,
-                       hits: bool = False) -> torch.Tensor:
-    """The rows / cols entries' workspace (x3, hits: larger ones of their own)."""
-    if hits:
-        return Workspace.get(L.tt_inbatch_hits_workspace_size(R, C, E, int(x3)), device,
-                             "inbatch_hits_x3" if x3 else "inbatch_hits")
-    if x3:
-        return Workspace.get(L.tt_inbatch_x3_workspace_size(R, C, E), device, "inbatch_x3")
-    return Workspace.get(L.tt_inbatch_workspace_size(R, C, E), device, "inbatch")
 
 
 def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
@@ -943,43 +938,16 @@ def inbatch_cols(q: torch.Tensor, lse: torch.Tensor, c: torch.Tensor, logq: Opti
     positive term (tt_inbatch_xent_cols_mixed; ids and thr as above, or
     none)."""
     hits = _ids_pair(row_ids, col_ids, q, c)
-    _req(q, "q", torch.float32, 2)
-    _req(c, "c", torch.float32, 2)
-    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
-    R, E = q.shape
-    C = c.shape[0]
+    ldq, ldc, R, C, E = _inbatch_operands(q, c, shapes=None)  # (c's width is the library's to check, as ldc)
     L = lib()
-    dc = torch.empty(C, E, dtype=torch.float32, device=q.device)
-    if mixed:
-        rid, cid = hits if hits is not None else (None, None)
-        ws = Workspace.get(L.tt_inbatch_mixed_workspace_size(R, C, E, int(x3)), q.device,
-                           "inbatch_mixed_x3" if x3 else "inbatch_mixed")
-        check(L.tt_inbatch_xent_cols_mixed(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
-                                           _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
-                                           _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3),
-                                           _opt_ptr(thr, "thr", R), dc.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _stream()))
-        return dc
-    if thr is not None:
-        rid, cid = hits if hits is not None else (None, None)
-        ws = _hard_workspace(L, R, C, E, q.device, x3)
-        check(L.tt_inbatch_xent_cols_hard(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
-                                          _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
-                                          _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3),
-                                          _opt_ptr(thr, "thr", R), dc.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream()))
-        return dc
-    ws = _inbatch_workspace(L, R, C, E, q.device, x3, hits is not None)
-    if hits is not None:
-        rid, cid = hits
-        check(L.tt_inbatch_xent_cols_hits(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R),
-                                          _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
-                                          _opt_ptr(logq, "logq", C), pos_offset, rid, cid, int(x3), dc.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _stream()))
-        return dc
-    fn = L.tt_inbatch_xent_cols_x3 if x3 else L.tt_inbatch_xent_cols
-    check(fn(q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
-             _opt_ptr(logq, "logq", C), pos_offset, dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    dc = _empty(q.device, C, E)
+    suffix, ws, mid = _inbatch_variant(L, R, C, E, q.device, x3, hits, hard=thr is not None, mixed=mixed)
+    head = (q.data_ptr(), ldq, R, _opt_ptr(lse, "lse", R), _opt_ptr(row_loss, "row_loss", R), c.data_ptr(), ldc, C, E,
+            _opt_ptr(logq, "logq", C), pos_offset)
+    if mixed or thr is not None:  # (the mixed entry takes thr or NULL)
+        mid += (_opt_ptr(thr, "thr", R),)
+    check(getattr(L, "tt_inbatch_xent_cols" + suffix)(*head, *mid, dc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _stream()))
     return dc
 
 
@@ -1057,74 +1025,38 @@ def inbatch_fused(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor]
         if prepped:
             raise ValueError("ids: the accidental-hit entry prepares its operands itself (prepped=False)")
         idp = _ids_ptr(ids, "ids", q)
-    _req(q, "q", torch.float32, 2)
-    _req(c, "c", torch.float32, 2)
-    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
-    B, E = q.shape
-    if tuple(c.shape) != (B, E):
-        raise ValueError("q and c must both be [B, E]")
+    ldq, ldc, B, _, E = _inbatch_operands(q, c, shapes="square")
     if prepped and ws is None:
         raise ValueError("prepped=True needs the workspace the operands were prepared into")
     L = lib()
-    if hard_k is not None:
-        ws = Workspace.get(L.tt_inbatch_fused_hard_workspace_size(B, E, int(x3)), q.device,
-                           "inbatch_fused_hard_x3" if x3 else "inbatch_fused_hard")
-        lse = torch.empty(B, dtype=torch.float32, device=q.device)
-        row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
-        dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
-        dc = torch.empty(B, E, dtype=torch.float32, device=q.device)
-        thr = torch.empty(B, dtype=torch.float32, device=q.device)
-        loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
-        check(L.tt_inbatch_softmax_xent_hard(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
-                                             idp if ids is not None else None, int(x3), hard_k, lse.data_ptr(),
-                                             row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(), thr.data_ptr(),
-                                             float(loss_scale if loss_scale is not None else 1.0),
-                                             loss.data_ptr() if loss is not None else None, ws.data_ptr(),
-                                             ws.numel(), _stream()))
-        return (lse, row_loss, dq, dc, thr, loss) if loss is not None else (lse, row_loss, dq, dc, thr)
-    if ids is not None:
-        ws = Workspace.get(L.tt_inbatch_fused_hits_workspace_size(B, E, int(x3)), q.device,
-                           "inbatch_fused_hits_x3" if x3 else "inbatch_fused_hits")
-        lse = torch.empty(B, dtype=torch.float32, device=q.device)
-        row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
-        dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
-        dc = torch.empty(B, E, dtype=torch.float32, device=q.device)
-        loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
-        check(L.tt_inbatch_softmax_xent_hits(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
-                                             idp, int(x3), lse.data_ptr(), row_loss.data_ptr(), dq.data_ptr(),
-                                             dc.data_ptr(), float(loss_scale if loss_scale is not None else 1.0),
-                                             loss.data_ptr() if loss is not None else None, ws.data_ptr(),
-                                             ws.numel(), _stream()))
-        return (lse, row_loss, dq, dc, loss) if loss is not None else (lse, row_loss, dq, dc)
-    if x3:
+    kind = "hard" if hard_k is not None else "hits" if ids is not None else "x3" if x3 else None
+    if kind == "x3":
         if prepped:
             raise ValueError("x3: the fp32-faithful entry prepares its operands itself (prepped=False)")
         ws = Workspace.get(L.tt_inbatch_fused_x3_workspace_size(B, E), q.device, "inbatch_fused_x3")
-    if ws is None:
+    elif kind is not None:  # (each with a workspace of its own, whatever ws is)
+        ws = Workspace.get(getattr(L, f"tt_inbatch_fused_{kind}_workspace_size")(B, E, int(x3)), q.device,
+                           f"inbatch_fused_{kind}" + ("_x3" if x3 else ""))
+    elif ws is None:
         ws = inbatch_fused_workspace(B, E, q.device)
-    lse = torch.empty(B, dtype=torch.float32, device=q.device)
-    row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
-    dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
-    dc = torch.empty(B, E, dtype=torch.float32, device=q.device)
-    if x3:
-        loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
-        check(L.tt_inbatch_softmax_xent_x3(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
-                                           lse.data_ptr(), row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(),
-                                           float(loss_scale if loss_scale is not None else 1.0),
-                                           loss.data_ptr() if loss is not None else None, ws.data_ptr(), ws.numel(),
-                                           _stream()))
-        return (lse, row_loss, dq, dc, loss) if loss is not None else (lse, row_loss, dq, dc)
-    if loss_scale is not None:
-        loss = torch.empty((), dtype=torch.float32, device=q.device)
-        check(L.tt_inbatch_softmax_xent_loss(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B),
-                                             lse.data_ptr(), row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(),
-                                             float(loss_scale), loss.data_ptr(), int(prepped), ws.data_ptr(),
-                                             ws.numel(), _stream()))
-        return lse, row_loss, dq, dc, loss
-    fn = L.tt_inbatch_softmax_xent_prepped if prepped else L.tt_inbatch_softmax_xent
-    check(fn(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B), lse.data_ptr(), row_loss.data_ptr(),
-             dq.data_ptr(), dc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-    return lse, row_loss, dq, dc
+    lse, row_loss, dq, dc = _empty(q.device, B), _empty(q.device, B), _empty(q.device, B, E), _empty(q.device, B, E)
+    thr = _empty(q.device, B) if hard_k is not None else None
+    loss = _empty(q.device) if loss_scale is not None else None
+    # (loss_scale, loss): after the outputs of every entry but the plain and the prepped one
+    sl = (float(loss_scale if loss_scale is not None else 1.0), loss.data_ptr() if loss is not None else None)
+    # the entry, its arguments between logq and the outputs, and between the outputs and the workspace
+    fn, mid, end = {
+        "hard": (L.tt_inbatch_softmax_xent_hard, (idp if ids is not None else None, int(x3), hard_k),
+                 (thr.data_ptr() if thr is not None else None, *sl)),
+        "hits": (L.tt_inbatch_softmax_xent_hits, (idp if ids is not None else None, int(x3)), sl),
+        "x3": (L.tt_inbatch_softmax_xent_x3, (), sl),
+        "loss": (L.tt_inbatch_softmax_xent_loss, (), (*sl, int(prepped))),
+        "prepped": (L.tt_inbatch_softmax_xent_prepped, (), ()),
+        "plain": (L.tt_inbatch_softmax_xent, (), ()),
+    }[kind or ("loss" if loss is not None else "prepped" if prepped else "plain")]
+    check(fn(q.data_ptr(), ldq, c.data_ptr(), ldc, B, E, _opt_ptr(logq, "logq", B), *mid, lse.data_ptr(),
+             row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(), *end, ws.data_ptr(), ws.numel(), _stream()))
+    return (lse, row_loss, dq, dc) + ((thr,) if thr is not None else ()) + ((loss,) if loss is not None else ())
 
 
 def inbatch_fused_mixed(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor],
@@ -1138,22 +1070,14 @@ def inbatch_fused_mixed(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.T
     if hard_k is not None:
         hard_k = _hard_k(hard_k)
     idp = _ids_ptr(ids, "ids", c) if ids is not None else None
-    _req(q, "q", torch.float32, 2)
-    _req(c, "c", torch.float32, 2)
-    ldq, ldc = _row_major(q, "q"), _row_major(c, "c")
-    B, E = q.shape
-    M = c.shape[0] - B
-    if c.shape[1] != E or M < 0:
-        raise ValueError(f"c must be [B + M, E] with M >= 0 for q [B, E], got {tuple(c.shape)} for {tuple(q.shape)}")
+    ldq, ldc, B, C, E = _inbatch_operands(q, c, shapes="mixed")
+    M = C - B
     L = lib()
     ws = Workspace.get(L.tt_inbatch_fused_mixed_workspace_size(B, M, E, int(x3)), q.device,
                        "inbatch_fused_mixed_x3" if x3 else "inbatch_fused_mixed")
-    lse = torch.empty(B, dtype=torch.float32, device=q.device)
-    row_loss = torch.empty(B, dtype=torch.float32, device=q.device)
-    dq = torch.empty(B, E, dtype=torch.float32, device=q.device)
-    dc = torch.empty(B + M, E, dtype=torch.float32, device=q.device)
-    thr = torch.empty(B, dtype=torch.float32, device=q.device) if hard_k is not None else None
-    loss = torch.empty((), dtype=torch.float32, device=q.device) if loss_scale is not None else None
+    lse, row_loss, dq, dc = _empty(q.device, B), _empty(q.device, B), _empty(q.device, B, E), _empty(q.device, C, E)
+    thr = _empty(q.device, B) if hard_k is not None else None
+    loss = _empty(q.device) if loss_scale is not None else None
     check(L.tt_inbatch_softmax_xent_mixed(q.data_ptr(), ldq, B, c.data_ptr(), ldc, M, E,
                                           _opt_ptr(logq, "logq", B + M), idp, int(x3), hard_k or 0, lse.data_ptr(),
                                           row_loss.data_ptr(), dq.data_ptr(), dc.data_ptr(),
@@ -1161,8 +1085,7 @@ def inbatch_fused_mixed(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.T
                                           float(loss_scale if loss_scale is not None else 1.0),
                                           loss.data_ptr() if loss is not None else None, ws.data_ptr(), ws.numel(),
                                           _stream()))
-    out = (lse, row_loss, dq, dc) + ((thr,) if thr is not None else ()) + ((loss,) if loss is not None else ())
-    return out
+    return (lse, row_loss, dq, dc) + ((thr,) if thr is not None else ()) + ((loss,) if loss is not None else ())
 
 
 # --------------------------------------------------------------------------

@@ -84,9 +84,10 @@ def x3_scores() -> bool:
 # "mixed negatives").  c with len(q) rows issues the calls it always issued.
 
 
-def _row_ids(ids, q):
-    """The rows' ids of a loss whose ids cover every column: the first len(q)."""
-    return None if ids is None else ids[:q.shape[0]]
+def _row_ids(ids, q, c):
+    """The rows' ids of a loss whose ids cover every column: with extra
+    negatives the first len(q), otherwise ids as it is."""
+    return ids if ids is None or c.shape[0] == q.shape[0] else ids[:q.shape[0]]
 
 
 def _check_hard(k):
@@ -100,27 +101,38 @@ def weighted_inbatch_grads(q, c, logq, weights, ids=None, x3: Optional[bool] = N
     """(wloss [B], dq, dc) of the weighted single-device loss: rows, fold,
     cols, with the operands and ids the unweighted entries take;
     num_hard_negatives: select, rows, fold, cols."""
-    x3 = x3_scores() if x3 is None else x3
-    if c.shape[0] != q.shape[0]:  # extra negatives: (select,) rows, fold, the MIXED cols pass
-        rid = _row_ids(ids, q)
-        thr = None
-        if _check_hard(num_hard_negatives) is not None:
-            thr = hip_ops.inbatch_hard_threshold(q, c, logq, num_hard_negatives, x3=x3, row_ids=rid, col_ids=ids)
-        lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=rid, col_ids=ids, thr=thr)
-        lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
-        dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=rid, col_ids=ids, thr=thr,
-                                  mixed=True)
-        return wloss, dq, dc
-    if _check_hard(num_hard_negatives) is None:
-        lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids)
-        lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
-        dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids)
-        return wloss, dq, dc
-    thr = hip_ops.inbatch_hard_threshold(q, c, logq, num_hard_negatives, x3=x3, row_ids=ids, col_ids=ids)
-    lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, x3=x3, row_ids=ids, col_ids=ids, thr=thr)
+    hard = _check_hard(num_hard_negatives)
+    kw = {"x3": x3_scores() if x3 is None else x3, "row_ids": _row_ids(ids, q, c), "col_ids": ids}
+    if hard is not None:
+        kw["thr"] = hip_ops.inbatch_hard_threshold(q, c, logq, hard, **kw)
+    lse, row_loss, dq = hip_ops.inbatch_rows(q, c, logq, **kw)
     lse_w, row_loss_w, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss, dq)
-    dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, x3=x3, row_ids=ids, col_ids=ids, thr=thr)
+    if c.shape[0] != q.shape[0]:  # extra negatives: the MIXED cols pass
+        kw["mixed"] = True
+    dc = hip_ops.inbatch_cols(q, lse_w, c, logq, row_loss=row_loss_w, **kw)
     return wloss, dq, dc
+
+
+def _fused_grads(q, c, logq, ids, hard, x3, loss_scale=None, ws=None):
+    """(row_loss, dq, dc, loss) of the unweighted single-device loss through
+    the fused entries, whichever they return beside these: inbatch_fused, or
+    inbatch_fused_mixed where c has extra negatives (every option, its own
+    preparation and workspace).  loss_scale: the loss summed by an extra
+    workgroup of the entry's last launch (no tt_sum launch after it), else
+    loss is None.  ws: the workspace both operands were already prepared into
+    (hip_ops.inbatch_prep; the plain bf16 entry alone takes one)."""
+    kw = {}
+    if hard is not None:
+        kw["hard_k"] = hard
+    if loss_scale is not None:
+        kw["loss_scale"] = loss_scale
+    if c.shape[0] != q.shape[0]:
+        out = hip_ops.inbatch_fused_mixed(q, c, logq, x3=x3, ids=ids, **kw)
+    else:
+        if ws is not None:
+            kw.update(ws=ws, prepped=True)
+        out = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids, **kw)
+    return out[1], out[2], out[3], (out[-1] if loss_scale is not None else None)
 
 
 class _InBatchXent(torch.autograd.Function):
@@ -129,12 +141,8 @@ class _InBatchXent(torch.autograd.Function):
         if weights is not None:
             scale = scale * weight_scale
             row_loss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
-        elif c.shape[0] != q.shape[0]:  # extra negatives
-            _, row_loss, dq, dc = hip_ops.inbatch_fused_mixed(q, c, logq, x3=x3_scores(), ids=ids, hard_k=hard)[:4]
-        elif hard is not None:
-            _, row_loss, dq, dc, _ = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids, hard_k=hard)
         else:
-            lse, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3_scores(), ids=ids)
+            row_loss, dq, dc, _ = _fused_grads(q, c, logq, ids, hard, x3_scores())
         ctx.scale = scale
         ctx.save_for_backward(dq, dc)
         return hip_ops.loss_sum(row_loss, scale)
@@ -320,20 +328,8 @@ class _TowersInBatchXent(torch.autograd.Function):
         if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
             wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
             loss = hip_ops.loss_sum(wloss, scale)
-        elif c.shape[0] != q.shape[0]:  # extra negatives (its own preparation and workspace), every option
-            out = hip_ops.inbatch_fused_mixed(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids, hard_k=hard)
-            dq, dc, loss = out[2], out[3], out[-1]
-        elif hard is not None:  # hard negatives (its own preparation and workspace), either arithmetic, ids or none
-            _, _, dq, dc, _, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids,
-                                                          hard_k=hard)
-        elif ids is not None:  # accidental hits removed (its own preparation and workspace), either arithmetic
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=x3_scores(), ids=ids)
-        elif x3_scores():  # fp32-faithful scores (its own preparation and workspace)
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, loss_scale=scale, x3=True)
-        else:
-            # the loss summed by an extra workgroup of the loss entry's last launch
-            # (tt_inbatch_softmax_xent_loss): no tt_sum launch after it
-            _, _, dq, dc, loss = hip_ops.inbatch_fused(q, c, logq, ws=ws, prepped=ws is not None, loss_scale=scale)
+        else:  # (ws: only the plain bf16 loss has its operands prepared on the towers' streams)
+            _, dq, dc, loss = _fused_grads(q, c, logq, ids, hard, x3_scores(), loss_scale=scale, ws=ws)
         unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
         ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
         return loss
@@ -410,11 +406,7 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
             and threshold is None and not getattr(comm, "always", False)):
         # one rank: its rows are every row and its columns every column — the
         # single-device entry (one shared preparation of q and c for both passes)
-        if hard is not None:
-            _, row_loss, dq, dc, _ = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids, hard_k=hard)
-            return row_loss, dq, dc
-        _, row_loss, dq, dc = hip_ops.inbatch_fused(q, c, logq, x3=x3, ids=ids)
-        return row_loss, dq, dc
+        return _fused_grads(q, c, logq, ids, hard, x3)[:3]
     if hard is not None and threshold is None:
         threshold = functools.partial(hip_ops.inbatch_hard_threshold, x3=x3)
     rows = rows or (functools.partial(hip_ops.inbatch_rows, x3=True) if x3 else hip_ops.inbatch_rows)
@@ -436,18 +428,14 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     if weights is not None:
         lse, row_loss_w, wloss = (fold or hip_ops.inbatch_weight_rows)(weights, lse, row_loss, dq)
     Qa = comm.all_gather(q)                                    # [G b, E]
-    if comm.world == 1 and not getattr(comm, "always", False):
-        lse_a, loss_a = lse, (row_loss if weights is None else row_loss_w)  # one rank: its rows are every row (no stack / split copies)
-        if hard is not None:
-            cols = functools.partial(cols, thr=thr)
-    elif hard is not None:
-        st = comm.all_gather(torch.stack([lse, row_loss if weights is None else row_loss_w, thr.to(lse.dtype)], 1))  # [G b, 3]: and every row's thr
-        lse_a, loss_a = st[:, 0].contiguous(), st[:, 1].contiguous()
-        cols = functools.partial(cols, thr=st[:, 2].contiguous())
-    else:
-        st = comm.all_gather(torch.stack([lse, row_loss if weights is None else row_loss_w], 1))  # [G b, 2]: every row's lse and loss
-        lse_a, loss_a = st[:, 0].contiguous(), st[:, 1].contiguous()
-    dc = cols(Qa, lse_a, c, logq, pos_offset=off, row_loss=loss_a)  # local columns, every row
+    # every row's scalars for the cols pass: lse, loss and, when mining, thr
+    per_row = [lse, row_loss if weights is None else row_loss_w] + ([thr] if hard is not None else [])
+    if comm.world > 1 or getattr(comm, "always", False):  # (one rank: its rows are every row, no stack / split copies)
+        st = comm.all_gather(torch.stack(per_row[:2] + [t.to(lse.dtype) for t in per_row[2:]], 1))  # [G b, 2 or 3]
+        per_row = [st[:, i].contiguous() for i in range(len(per_row))]
+    if hard is not None:
+        cols = functools.partial(cols, thr=per_row[2])
+    dc = cols(Qa, per_row[0], c, logq, pos_offset=off, row_loss=per_row[1])  # local columns, every row
     return (row_loss if weights is None else wloss), dq, dc
 
 
@@ -546,14 +534,10 @@ def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     hard = _check_hard(num_hard_negatives)
     if not q.requires_grad and not c.requires_grad:
         # the scores the training loss is computed from, in either mode
-        rid = ids if c.shape[0] == q.shape[0] else _row_ids(ids, q)  # (extra negatives: the rows entries as they are)
+        kw = {"x3": x3_scores(), "row_ids": _row_ids(ids, q, c), "col_ids": ids}  # (extra negatives: the rows entries as they are)
         if hard is not None:
-            thr = hip_ops.inbatch_hard_threshold(q, c, logq, hard, x3=x3_scores(), row_ids=rid, col_ids=ids)
-            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=rid,
-                                                    col_ids=ids, thr=thr)
-        else:
-            lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, x3=x3_scores(), row_ids=rid,
-                                                    col_ids=ids)
+            kw["thr"] = hip_ops.inbatch_hard_threshold(q, c, logq, hard, **kw)
+        lse, row_loss, _ = hip_ops.inbatch_rows(q, c, logq, want_dq=False, **kw)
         if weights is not None:
             _, _, wloss = hip_ops.inbatch_weight_rows(weights, lse, row_loss)
             return hip_ops.loss_sum(wloss, scale * weight_scale)
