@@ -1577,15 +1577,16 @@ __global__ void __launch_bounds__(NW * kWave) finalize_kernel(const FinalArgs a)
 }
 
 // Exact fallback for the queries the finalize could not certify.  A
-// persistent grid of 4-wave workgroups takes work items from a global
+// persistent grid of FW-wave workgroups (4; fewer for large k, whose per-wave
+// lists would not fit the LDS: fallback_plan) takes work items from a global
 // counter: item (f, p) scans part p of the candidate rows for failed query f
-// with the fp32 chain (wave w takes the part's 64-row chunks w, w + 4, ... in
+// with the fp32 chain (wave w takes the part's 64-row chunks w, w + FW, ... in
 // index order, so a strict threshold at its running K-th score is exact),
 // merges its waves' exact top-K lists and writes them to scratch slot (f, p);
 // the workgroup that completes a query's last part merges the P lists and
 // writes the answer.  Queries beyond the scratch slots are scanned whole by
 // one workgroup.
-constexpr int kFbWaves = 4;
+constexpr int kFbWaves = 4;          // waves per workgroup while their lists fit the LDS
 constexpr int kFbSlots = 1024;       // failed queries served by the parallel form per chunk
 constexpr int kFbGrid = 512;         // persistent workgroups
 
@@ -1600,7 +1601,7 @@ struct FallbackArgs {
   int k;
   int L;              // per-wave list capacity
   int P;              // bitonic sort size
-  int parts;          // candidate parts per failed query (parts * k <= 8192)
+  int parts;          // candidate parts per failed query (parts * k <= 8192; the plan's, or fewer: fallback_plan)
   int vec4;
   const int* fail_count;
   const int* fail_list;
@@ -1611,15 +1612,16 @@ struct FallbackArgs {
   int32_t* out_i;
 };
 
-__host__ __device__ inline int fallback_merge_cap(int parts, int k) {
-  return parts * k > kFbWaves * k ? parts * k : kFbWaves * k;
+__host__ __device__ inline int fallback_merge_cap(int parts, int k, int waves = kFbWaves) {
+  return parts * k > waves * k ? parts * k : waves * k;
 }
-__host__ __device__ inline size_t fallback_lds_bytes(int L, int P, int parts, int k) {
-  return 128 * sizeof(float) + static_cast<size_t>(kFbWaves) * (static_cast<size_t>(L) * 8 + 256 * sizeof(unsigned)) +
-         static_cast<size_t>(fallback_merge_cap(parts, k)) * 8 + static_cast<size_t>(P) * 8 + 16 * sizeof(int);
+__host__ __device__ inline size_t fallback_lds_bytes(int L, int P, int parts, int k, int waves = kFbWaves) {
+  return 128 * sizeof(float) + static_cast<size_t>(waves) * (static_cast<size_t>(L) * 8 + 256 * sizeof(unsigned)) +
+         static_cast<size_t>(fallback_merge_cap(parts, k, waves)) * 8 + static_cast<size_t>(P) * 8 + 16 * sizeof(int);
 }
 
-__global__ void __launch_bounds__(kFbWaves * kWave) fallback_kernel(const FallbackArgs a) {
+template <int FW>
+__global__ void __launch_bounds__(FW * kWave) fallback_kernel(const FallbackArgs a) {
   extern __shared__ __attribute__((aligned(16))) char fsm[];
   const int wave = threadIdx.x / kWave;
   const int lane = lane_id();
@@ -1629,12 +1631,12 @@ __global__ void __launch_bounds__(kFbWaves * kWave) fallback_kernel(const Fallba
   float* sc = reinterpret_cast<float*>(wbase);
   unsigned* id = reinterpret_cast<unsigned*>(sc + a.L);
   unsigned* hist = id + a.L;
-  const int MC = fallback_merge_cap(PT, K);
-  char* mbase = fsm + 128 * sizeof(float) + static_cast<size_t>(kFbWaves) * (static_cast<size_t>(a.L) * 8 + 1024);
+  const int MC = fallback_merge_cap(PT, K, FW);
+  char* mbase = fsm + 128 * sizeof(float) + static_cast<size_t>(FW) * (static_cast<size_t>(a.L) * 8 + 1024);
   float* msc = reinterpret_cast<float*>(mbase);
   unsigned* mid = reinterpret_cast<unsigned*>(msc + MC);
   unsigned long long* sk = reinterpret_cast<unsigned long long*>(mid + MC);
-  int* sh = reinterpret_cast<int*>(sk + a.P);  // [0] item, [1..4] wave counts, [5] merge flag
+  int* sh = reinterpret_cast<int*>(sk + a.P);  // [0] item, [1..FW] wave counts, [5] merge flag
   const int nf = *a.fail_count;
   const int npar = nf < kFbSlots ? nf : kFbSlots;
   const int total = npar * PT + (nf - npar);
@@ -1654,7 +1656,7 @@ __global__ void __launch_bounds__(kFbWaves * kWave) fallback_kernel(const Fallba
     __syncthreads();
     float ethr = -INFINITY;
     int n = 0;
-    for (int64_t c0 = r0 + static_cast<int64_t>(wave) * kWave; c0 < r1; c0 += kFbWaves * kWave) {
+    for (int64_t c0 = r0 + static_cast<int64_t>(wave) * kWave; c0 < r1; c0 += FW * kWave) {
       const int64_t c = c0 + lane;
       float sv = -INFINITY;
       if (c < r1) sv = exact_score(qs, a.cand + c * a.ldc, a.dim, a.vec4 != 0) + 0.0f;
@@ -1682,7 +1684,7 @@ __global__ void __launch_bounds__(kFbWaves * kWave) fallback_kernel(const Fallba
     __syncthreads();
     if (wave == 0) {
       int nm = sh[1];
-      for (int w = 1; w < kFbWaves; ++w) {  // compact the wave lists to the front
+      for (int w = 1; w < FW; ++w) {  // compact the wave lists to the front
         const int cw = sh[1 + w];
         for (int j0 = 0; j0 < cw; j0 += kWave) {
           const int j = j0 + lane;
@@ -1940,9 +1942,38 @@ int run_scan(int D, const void* index, int64_t row0, int64_t row1, int64_t nq, c
   return run_pass(D, sa, nq_pad, false, st);
 }
 
+// The LDS one workgroup may ask for (160 KiB per CU): a plan beyond it is a
+// message, never a launch attempt.
+constexpr size_t kLdsLimit = 160 * 1024;
+
+// What the fallback is launched with.  Up to k = 1120 that is the plan's L /
+// parts on 4 waves.  Above (but for 1171..1184, where parts has just dropped
+// to 6), 4 per-wave lists of 2k + 256 entries plus the merge buffer pass the
+// LDS limit, so the workgroup shrinks to the most waves (4, 2, 1) that fit
+// with the plan's parts, and past that (k >= 3969) to the most parts that fit
+// one wave: at k = 4000 one wave, one part, 132,416 B.  Fewer parts use a
+// prefix of the scratch the plan sized, so the workspace does not change.
+struct FallbackPlan {
+  int waves, parts;
+  size_t lds;
+};
+FallbackPlan fallback_plan(const SearchPlan& p) {
+  FallbackPlan f{kFbWaves, p.parts, fallback_lds_bytes(p.L, p.P, p.parts, p.k, kFbWaves)};
+  while (f.lds > kLdsLimit && f.waves > 1) {
+    f.waves /= 2;
+    f.lds = fallback_lds_bytes(p.L, p.P, f.parts, p.k, f.waves);
+  }
+  while (f.lds > kLdsLimit && f.parts > 1) {
+    --f.parts;
+    f.lds = fallback_lds_bytes(p.L, p.P, f.parts, p.k, f.waves);
+  }
+  return f;
+}
+
 template <int NW>
 int launch_finalize_nw(const FinalArgs& fa, int64_t nq, const SearchPlan& p, hipStream_t st) {
   const size_t shm = final_lds_bytes(p.LF, p.P, NW);
+  TT_REQUIRE(shm <= kLdsLimit, "bruteforce finalize: k=%d needs %zu bytes of LDS > %zu", p.k, shm, kLdsLimit);
   if (shm > 65536)
     TT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel<NW>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(shm)));
@@ -1959,17 +1990,30 @@ int launch_finalize(const FinalArgs& fa, int64_t nq, const SearchPlan& p, hipStr
   }
 }
 
-int run_finalize(const FinalArgs& fa, const FallbackArgs& fb, int64_t nq, const SearchPlan& p, hipStream_t st) {
-  const size_t fshm = fallback_lds_bytes(p.L, p.P, p.parts, p.k);
+template <int FW>
+int launch_fallback_fw(const FallbackArgs& fb, size_t fshm, hipStream_t st) {
   if (fshm > 65536)
-    TT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fallback_kernel),
+    TT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fallback_kernel<FW>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fshm)));
+  hipLaunchKernelGGL(fallback_kernel<FW>, dim3(kFbGrid), dim3(FW * kWave), fshm, st, fb);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+// fb carries the plan's parts; the fallback runs with fallback_plan's
+int run_finalize(const FinalArgs& fa, const FallbackArgs& fb_in, int64_t nq, const SearchPlan& p, hipStream_t st) {
+  const FallbackPlan f = fallback_plan(p);
+  TT_REQUIRE(f.lds <= kLdsLimit, "bruteforce fallback: k=%d needs %zu bytes of LDS > %zu", p.k, f.lds, kLdsLimit);
+  FallbackArgs fb = fb_in;
+  fb.parts = f.parts;
   probe_begin(TT_PROBE_INDEX_FINALIZE, st);
   if (int rc = launch_finalize(fa, nq, p, st)) return rc;
   probe_end(TT_PROBE_INDEX_FINALIZE, st);
-  hipLaunchKernelGGL(fallback_kernel, dim3(kFbGrid), dim3(kFbWaves * kWave), fshm, st, fb);
-  TT_CHECK_LAUNCH();
-  return TT_OK;
+  switch (f.waves) {
+    case 4: return launch_fallback_fw<4>(fb, f.lds, st);
+    case 2: return launch_fallback_fw<2>(fb, f.lds, st);
+    default: return launch_fallback_fw<1>(fb, f.lds, st);
+  }
 }
 
 inline const float2* index_norms(const void* index, int64_t n_cand, int D) {
@@ -2017,6 +2061,12 @@ extern "C" size_t tt_bruteforce_workspace_size(int64_t n_queries, int64_t n_cand
   Carver cv(nullptr, 0);
   carve_search(cv, pick_dpad(dim), p, true, true);
   return cv.used();
+}
+
+extern "C" size_t tt_bruteforce_lds_bytes(int32_t k, int32_t which) {
+  if (k < 1 || k > 4000 || (which != 0 && which != 1)) return 0;
+  const SearchPlan p = plan_search(1, k, k, 1);  // L, LF, P, NW, parts depend on k alone
+  return which == 0 ? final_lds_bytes(p.LF, p.P, p.NW) : fallback_plan(p).lds;
 }
 
 extern "C" int tt_bruteforce_search(const void* index, const float* cand, int64_t ldc, int64_t n_cand, int32_t dim,

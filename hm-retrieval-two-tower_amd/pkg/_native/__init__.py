@@ -418,6 +418,7 @@ _PROTOS = {
     "tt_bruteforce_index_bytes": (c_size_t, [c_int64, c_int32]),
     "tt_bruteforce_build": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "tt_bruteforce_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "tt_bruteforce_lds_bytes": (c_size_t, [c_int32, c_int32]),
     "tt_bruteforce_search": (
         c_int32,
         [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p,

@@ -694,6 +694,10 @@ int tt_bruteforce_build(const float* cand, int64_t ldc, int64_t n_cand,
                         tt_stream_t stream);
 size_t tt_bruteforce_workspace_size(int64_t n_queries, int64_t n_cand,
                                     int32_t dim, int32_t k);
+/* Host-only: dynamic LDS bytes a search at this k asks of one workgroup, for
+ * the finalize (which = 0) or the exact fallback (which = 1); at most 163840
+ * for every k in [1, 4000].  0: k or which out of range. */
+size_t tt_bruteforce_lds_bytes(int32_t k, int32_t which);
 int tt_bruteforce_search(const void* index, const float* cand, int64_t ldc,
                          int64_t n_cand, int32_t dim, const float* queries,
                          int64_t ldq, int64_t n_queries, int32_t k,

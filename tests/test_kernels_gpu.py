@@ -2,6 +2,11 @@
 
 Tolerances:
   gather, dedup, Adagrad, top-k indices + scores, merge, recall: bit-exact.
+  The index beyond the shapes here (k up to 4000, dims that are no multiple
+    of 4, unaligned and pitched rows, more failed queries than fallback
+    slots, mixed bound modes, ordered candidates), bit-exact as well:
+    tests/test_index_edges_gpu.py (inputs: tests/index_cases.py, checked on
+    the CPU with the host plan by tests/test_index_edges_host.py).
   Adam (sparse and dense): here rtol 2e-6 / atol 1e-7 with the default betas
     (0.9, 0.999: lr_t holds the host's powf, which may differ from numpy's in
     the last bit); bit-exact in table / p, m and v with betas (0.5, 0.75),
