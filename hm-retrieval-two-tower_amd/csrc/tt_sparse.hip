@@ -54,6 +54,7 @@
 // rounded fp32 divide/sqrt) so results match the CPU restatement bit for bit.
 // (HIP's __fsqrt_rn maps to the approximate native sqrt on this toolchain.)
 #include <algorithm>
+#include <cmath>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "tt_common.h"
@@ -1194,6 +1195,132 @@ __global__ void dense_adam_kernel(float* p, float* m, float* v, const float* g, 
   }
 }
 
+// ---- Adam with the step count in device memory (tt_adam_clock) ------------
+// The host entries above take `step` and compute their coefficient with the
+// host's powf; a captured graph cannot.  The _dev entries read the step's
+// coefficients from a tt_adam_clock that one tiny launch advances from a
+// host-filled table (tt_adam_coef_fill), so a replay takes the next step's
+// pair without any host work, and the pair is the host entries' to the bit.
+__global__ void adam_clock_kernel(tt_adam_clock* c, const float* alpha_tab, const float* lr_t_tab, int64_t len) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t s = c->step + 1;
+  int64_t k = (s < len ? s : len) - 1;  // past the table's end both coefficients stay at its last entry
+  if (k < 0) k = 0;
+  c->step = s;
+  c->alpha = alpha_tab[k];
+  c->lr_t = lr_t_tab[k];
+}
+
+// dense_adam_kernel on up to kDenseMaxJobs buffers in one launch, alpha from
+// the clock (dense_adagrad_many_kernel's loop over the concatenation)
+struct DenseAdamJobs {
+  float* p[kDenseMaxJobs];
+  float* m[kDenseMaxJobs];
+  float* v[kDenseMaxJobs];
+  const float* g[kDenseMaxJobs];
+  int64_t begin[kDenseMaxJobs + 1];
+  int num;
+  float omb1, omb2, eps;
+  const tt_adam_clock* clock;
+};
+__global__ void dense_adam_many_dev_kernel(const DenseAdamJobs d) {
+  const int64_t total = d.begin[d.num];
+  const float alpha = d.clock->alpha;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int t = 0;
+#pragma unroll 1
+    for (int q = 1; q < d.num; ++q)
+      if (i >= d.begin[q]) t = q;
+    const int64_t k = i - d.begin[t];
+    const float gi = d.g[t][k];
+    const float m0 = d.m[t][k], v0 = d.v[t][k];
+    const float mi = ieee_op<'+'>(m0, ieee_op<'*'>(ieee_op<'-'>(gi, m0), d.omb1));
+    const float vi = ieee_op<'+'>(v0, ieee_op<'*'>(ieee_op<'-'>(ieee_op<'*'>(gi, gi), v0), d.omb2));
+    d.m[t][k] = mi;
+    d.v[t][k] = vi;
+    d.p[t][k] = ieee_op<'-'>(d.p[t][k], ieee_op<'/'>(ieee_op<'*'>(mi, alpha), ieee_op<'+'>(sqrtf(vi), d.eps)));
+  }
+}
+
+// The two whole-table stages of the legacy sparse Adam step (scale2_kernel and
+// adam_var_kernel, the same per-element arithmetic) over up to kAdamMaxTables
+// tables in ONE launch each.  Pure streaming: a thread takes a unit of 4
+// consecutive elements of one table (found by a search over the prefix sums of
+// the tables' unit counts) with 16-byte accesses when the table's three bases
+// are 16-byte aligned; a table's last, shorter unit and unaligned tables take
+// the elements one by one.  The grid is capped at 8 blocks per CU and strides.
+constexpr int kAdamMaxTables = 16;
+constexpr int kAdamUnit = 4;
+constexpr int kAdamGridMax = 2048;
+struct AdamTables {
+  float* var[kAdamMaxTables];
+  float* m[kAdamMaxTables];
+  float* v[kAdamMaxTables];
+  int64_t n[kAdamMaxTables];          // elements
+  int64_t begin[kAdamMaxTables + 1];  // prefix sums of ceil(n / kAdamUnit)
+  uint32_t vec;                       // bit t: table t takes 16-byte accesses
+  int num;
+};
+
+__device__ __forceinline__ int adam_table_of(const AdamTables& d, int64_t u) {
+  int t = 0;
+#pragma unroll 1
+  for (int q = 1; q < d.num; ++q)
+    if (u >= d.begin[q]) t = q;
+  return t;
+}
+
+__global__ void __launch_bounds__(256) adam_decay_many_kernel(const AdamTables d, float b1, float b2) {
+  const int64_t total = d.begin[d.num];
+  for (int64_t u = blockIdx.x * (int64_t)256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int t = adam_table_of(d, u);
+    const int64_t e = (u - d.begin[t]) * kAdamUnit, left = d.n[t] - e;
+    float* m = d.m[t] + e;
+    float* v = d.v[t] + e;
+    if (((d.vec >> t) & 1u) && left >= kAdamUnit) {
+      f32x4 a = *reinterpret_cast<const f32x4*>(m), b = *reinterpret_cast<const f32x4*>(v);
+#pragma unroll
+      for (int c = 0; c < kAdamUnit; ++c) {
+        a[c] = ieee_op<'*'>(a[c], b1);
+        b[c] = ieee_op<'*'>(b[c], b2);
+      }
+      *reinterpret_cast<f32x4*>(m) = a;
+      *reinterpret_cast<f32x4*>(v) = b;
+    } else {
+      const int cnt = left < kAdamUnit ? static_cast<int>(left) : kAdamUnit;
+      for (int c = 0; c < cnt; ++c) {
+        m[c] = ieee_op<'*'>(m[c], b1);
+        v[c] = ieee_op<'*'>(v[c], b2);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) adam_var_many_kernel(const AdamTables d, const tt_adam_clock* clock,
+                                                            float eps) {
+  const int64_t total = d.begin[d.num];
+  const float lr = clock->lr_t;
+  for (int64_t u = blockIdx.x * (int64_t)256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+    const int t = adam_table_of(d, u);
+    const int64_t e = (u - d.begin[t]) * kAdamUnit, left = d.n[t] - e;
+    float* var = d.var[t] + e;
+    const float* m = d.m[t] + e;
+    const float* v = d.v[t] + e;
+    if (((d.vec >> t) & 1u) && left >= kAdamUnit) {
+      f32x4 x = *reinterpret_cast<const f32x4*>(var);
+      const f32x4 a = *reinterpret_cast<const f32x4*>(m), b = *reinterpret_cast<const f32x4*>(v);
+#pragma unroll
+      for (int c = 0; c < kAdamUnit; ++c)
+        x[c] = ieee_op<'-'>(x[c], ieee_op<'/'>(ieee_op<'*'>(lr, a[c]), ieee_op<'+'>(sqrtf(b[c]), eps)));
+      *reinterpret_cast<f32x4*>(var) = x;
+    } else {
+      const int cnt = left < kAdamUnit ? static_cast<int>(left) : kAdamUnit;
+      for (int c = 0; c < cnt; ++c)
+        var[c] = ieee_op<'-'>(var[c], ieee_op<'/'>(ieee_op<'*'>(lr, m[c]), ieee_op<'+'>(sqrtf(v[c]), eps)));
+    }
+  }
+}
+
 // Adagrad on rows that are distinct (tt_sparse_adagrad_rows): slot j applies
 // grad row j to row rows[j] of table tags[j]; one thread per 4 columns of a
 // slot (dim % 4 == 0) or per column.  g = 0 + (0 + grad): the block sums'
@@ -1349,6 +1476,56 @@ dim3 stride_grid(int64_t n) {
   return dim3(static_cast<unsigned>(b));
 }
 
+// The step-dependent part of Adam, in fp32 with the host's powf: the ONE place
+// the coefficients are computed (tt_dense_adam, tt_sparse_adam and the table
+// fill of the device clock all call it).
+//   alpha: TF ApplyAdamOp, (lr * sqrt(1 - beta2^t)) / (1 - beta1^t)
+//   lr_t:  legacy Adam._prepare_local, lr * (sqrt(1 - beta2^t) / (1 - beta1^t))
+// saturated: 1 - beta^t == 1 for both betas, so both coefficients are lr itself.
+struct AdamCoef {
+  float alpha, lr_t;
+  bool saturated;
+};
+AdamCoef adam_coef(float lr, float beta1, float beta2, int64_t step) {
+  const float b1p = powf(beta1, static_cast<float>(step));
+  const float b2p = powf(beta2, static_cast<float>(step));
+  const float rad = 1.0f - b2p, den = 1.0f - b1p;
+  AdamCoef c;
+  c.alpha = (lr * sqrtf(rad)) / den;
+  c.lr_t = lr * (sqrtf(rad) / den);
+  c.saturated = rad == 1.0f && den == 1.0f;
+  return c;
+}
+
+bool adam_beta_ok(float b) { return b >= 0.0f && b < 1.0f; }  // false for NaN
+
+constexpr int64_t kAdamCoefMaxLen = int64_t(1) << 22;
+
+// Whole-table launches of tt_sparse_adam_dev over tables [first, first + cnt).
+AdamTables adam_tables(const tt_sparse_table* tables, int cnt) {
+  AdamTables d{};
+  d.num = cnt;
+  int64_t units = 0;
+  for (int i = 0; i < cnt; ++i) {
+    const tt_sparse_table& t = tables[i];
+    d.var[i] = t.table;
+    d.m[i] = t.slot0;
+    d.v[i] = t.slot1;
+    d.n[i] = t.num_rows * t.dim;
+    d.begin[i] = units;
+    units += ceil_div(d.n[i], static_cast<int64_t>(kAdamUnit));
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(t.table) | reinterpret_cast<uintptr_t>(t.slot0) |
+                           reinterpret_cast<uintptr_t>(t.slot1);
+    if (bits % 16 == 0) d.vec |= 1u << i;
+  }
+  d.begin[cnt] = units;
+  return d;
+}
+
+dim3 adam_grid(int64_t units) {
+  return dim3(static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(ceil_div(units, int64_t(256)), 1), kAdamGridMax)));
+}
+
 }  // namespace
 }  // namespace tt
 
@@ -1415,9 +1592,7 @@ extern "C" int tt_sparse_adam(const tt_sparse_table* tables, int32_t num_tables,
   hipStream_t st = to_stream(stream);
   // Coefficients exactly as legacy Adam._prepare_local computes them in fp32.
   const float b1 = beta1, b2 = beta2;
-  const float b1p = powf(b1, static_cast<float>(step));
-  const float b2p = powf(b2, static_cast<float>(step));
-  const float lr_t = lr * (sqrtf(1.0f - b2p) / (1.0f - b1p));
+  const float lr_t = adam_coef(lr, beta1, beta2, step).lr_t;
   for (int i = 0; i < num_tables; ++i) {
     const int64_t n = tables[i].num_rows * tables[i].dim;
     hipLaunchKernelGGL(scale2_kernel, stride_grid(n), dim3(256), 0, st, tables[i].slot0, b1, tables[i].slot1, b2, n);
@@ -1572,13 +1747,109 @@ extern "C" int tt_dense_adam(float* param, float* m, float* v, const float* grad
   TT_REQUIRE(n >= 0 && step >= 1, "tt_dense_adam: bad n/step");
   if (n == 0) return TT_OK;
   TT_REQUIRE(param && m && v && grad, "tt_dense_adam: NULL pointer");
-  const float b1p = powf(beta1, static_cast<float>(step));
-  const float b2p = powf(beta2, static_cast<float>(step));
   // TF ApplyAdamOp: alpha = lr * sqrt(1 - beta2_power) / (1 - beta1_power).
-  const float alpha = (lr * sqrtf(1.0f - b2p)) / (1.0f - b1p);
+  const float alpha = adam_coef(lr, beta1, beta2, step).alpha;
   hipLaunchKernelGGL(dense_adam_kernel, stride_grid(n), dim3(256), 0, to_stream(stream), param, m, v, grad, n,
                      alpha, 1.0f - beta1, 1.0f - beta2, epsilon);
   TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int64_t tt_adam_coef_len(float beta1, float beta2) {
+  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return 0;
+  for (int64_t t = 1; t <= kAdamCoefMaxLen; ++t)
+    if (adam_coef(1.0f, beta1, beta2, t).saturated) return t;
+  return 0;
+}
+
+extern "C" int tt_adam_coef_fill(float lr, float beta1, float beta2, int64_t len, float* alpha, float* lr_t) {
+  clear_error();
+  TT_REQUIRE(std::isfinite(lr), "tt_adam_coef_fill: learning rate is not finite");
+  TT_REQUIRE(adam_beta_ok(beta1) && adam_beta_ok(beta2), "tt_adam_coef_fill: betas must lie in [0, 1), got %g / %g",
+             static_cast<double>(beta1), static_cast<double>(beta2));
+  TT_REQUIRE(len >= 1, "tt_adam_coef_fill: len must be >= 1");
+  TT_REQUIRE(alpha && lr_t, "tt_adam_coef_fill: NULL pointer");
+  for (int64_t t = 1; t <= len; ++t) {
+    const AdamCoef c = adam_coef(lr, beta1, beta2, t);
+    alpha[t - 1] = c.alpha;
+    lr_t[t - 1] = c.lr_t;
+  }
+  return TT_OK;
+}
+
+extern "C" int tt_adam_clock_advance(tt_adam_clock* clock, const float* alpha_tab, const float* lr_t_tab,
+                                     int64_t len, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(clock && alpha_tab && lr_t_tab, "tt_adam_clock_advance: NULL pointer");
+  TT_REQUIRE(len >= 1, "tt_adam_clock_advance: len must be >= 1");
+  hipLaunchKernelGGL(adam_clock_kernel, dim3(1), dim3(64), 0, to_stream(stream), clock, alpha_tab, lr_t_tab, len);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int tt_dense_adam_many_dev(const tt_dense_adam_job* jobs, int32_t num_jobs, float beta1, float beta2,
+                                      float epsilon, const tt_adam_clock* clock, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(jobs && num_jobs >= 1 && num_jobs <= kDenseMaxJobs, "tt_dense_adam_many_dev: 1..%d jobs, got %d",
+             kDenseMaxJobs, num_jobs);
+  TT_REQUIRE(clock, "tt_dense_adam_many_dev: NULL clock");
+  DenseAdamJobs d{};
+  d.num = num_jobs;
+  d.omb1 = 1.0f - beta1;
+  d.omb2 = 1.0f - beta2;
+  d.eps = epsilon;
+  d.clock = clock;
+  int64_t total = 0;
+  for (int i = 0; i < num_jobs; ++i) {
+    TT_REQUIRE(jobs[i].n >= 0, "tt_dense_adam_many_dev: job %d negative n", i);
+    TT_REQUIRE(jobs[i].n == 0 || (jobs[i].param && jobs[i].m && jobs[i].v && jobs[i].grad),
+               "tt_dense_adam_many_dev: job %d NULL pointer", i);
+    d.p[i] = jobs[i].param;
+    d.m[i] = jobs[i].m;
+    d.v[i] = jobs[i].v;
+    d.g[i] = jobs[i].grad;
+    d.begin[i] = total;
+    total += jobs[i].n;
+  }
+  d.begin[num_jobs] = total;
+  if (total == 0) return TT_OK;
+  hipLaunchKernelGGL(dense_adam_many_dev_kernel, stride_grid(total), dim3(256), 0, to_stream(stream), d);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int tt_sparse_adam_dev(const tt_sparse_table* tables, int32_t num_tables, int64_t batch,
+                                  const float* grad, int64_t grad_stride, float beta1, float beta2, float epsilon,
+                                  const tt_adam_clock* clock, void* workspace, size_t workspace_bytes,
+                                  tt_stream_t stream) {
+  clear_error();
+  int rc = validate_tables(tables, num_tables, batch, true);
+  if (rc) return rc;
+  TT_REQUIRE(clock, "tt_sparse_adam_dev: NULL clock");
+  const size_t need = tables_ws_bytes(tables, num_tables, batch, 0);
+  if (batch > 0 && (!workspace || workspace_bytes < need))
+    return fail(TT_ERR_WORKSPACE, "tt_sparse_adam_dev: workspace %zu < required %zu", workspace_bytes, need);
+  hipStream_t st = to_stream(stream);
+  // stage 1: every table's slots decayed, kAdamMaxTables tables a launch
+  for (int first = 0; first < num_tables; first += kAdamMaxTables) {
+    const AdamTables d = adam_tables(tables + first, std::min(num_tables - first, kAdamMaxTables));
+    hipLaunchKernelGGL(adam_decay_many_kernel, adam_grid(d.begin[d.num]), dim3(256), 0, st, d, beta1, beta2);
+    TT_CHECK_LAUNCH();
+  }
+  // stage 2: tt_sparse_adam's scatter, unchanged
+  if (batch > 0) {
+    ApplyParams ap{};
+    ap.one_minus_beta1 = 1.0f - beta1;
+    ap.one_minus_beta2 = 1.0f - beta2;
+    rc = run_sparse<kAdamScatter>(tables, num_tables, batch, grad, grad_stride, ap, workspace, workspace_bytes, st);
+    if (rc) return rc;
+  }
+  // stage 3: every table updated from its slots, lr_t read from the clock
+  for (int first = 0; first < num_tables; first += kAdamMaxTables) {
+    const AdamTables d = adam_tables(tables + first, std::min(num_tables - first, kAdamMaxTables));
+    hipLaunchKernelGGL(adam_var_many_kernel, adam_grid(d.begin[d.num]), dim3(256), 0, st, d, clock, epsilon);
+    TT_CHECK_LAUNCH();
+  }
   return TT_OK;
 }
 

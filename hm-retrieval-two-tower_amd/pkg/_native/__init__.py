@@ -19,6 +19,7 @@ __all__ = [
     "GatherCall",
     "RowTable",
     "SparseTable",
+    "DenseAdamJob",
     "RouteLookup",
     "MlpPackJob",
     "MlpRowsProblem",
@@ -230,6 +231,16 @@ class DenseJob(ctypes.Structure):
     ]
 
 
+class DenseAdamJob(ctypes.Structure):
+    _fields_ = [
+        ("param", c_void_p),
+        ("m", c_void_p),
+        ("v", c_void_p),
+        ("grad", c_void_p),
+        ("n", c_int64),
+    ]
+
+
 ROUTE_MAX_LOOKUPS = 32  # TT_ROUTE_MAX_LOOKUPS
 
 
@@ -315,6 +326,16 @@ _PROTOS = {
     "tt_dense_adam": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int64, c_void_p],
+    ),
+    "tt_adam_coef_len": (c_int64, [c_float, c_float]),
+    "tt_adam_coef_fill": (c_int32, [c_float, c_float, c_float, c_int64, c_void_p, c_void_p]),
+    "tt_adam_clock_advance": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "tt_dense_adam_many_dev": (c_int32, [POINTER(DenseAdamJob), c_int32, c_float, c_float, c_float, c_void_p,
+                                         c_void_p]),
+    "tt_sparse_adam_dev": (
+        c_int32,
+        [POINTER(SparseTable), c_int32, c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_void_p,
+         c_size_t, c_void_p],
     ),
     "tt_inbatch_workspace_size": (c_size_t, [c_int64, c_int64, c_int32]),
     "tt_inbatch_xent_rows": (

@@ -29,6 +29,11 @@ __all__ = [
     "dense_adagrad",
     "dense_adagrad_many",
     "dense_adam",
+    "adam_coef_len",
+    "adam_coef_tables",
+    "adam_clock_advance",
+    "dense_adam_many_dev",
+    "sparse_adam_dev",
     "inbatch_rows",
     "inbatch_hard_threshold",
     "inbatch_cols",
@@ -769,6 +774,76 @@ def dense_adam(param, m, v, grad, lr, beta1, beta2, epsilon, step) -> None:
             raise ValueError(f"{n} must be contiguous with param's numel")
     check(lib().tt_dense_adam(param.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), param.numel(), lr,
                               beta1, beta2, epsilon, step, _stream()))
+
+
+# -- Adam with the step count on the device (tt_adam_clock) -------------------
+def adam_coef_len(beta1: float, beta2: float) -> int:
+    """tt_adam_coef_len: the first step from which both Adam coefficients equal
+    the learning rate in fp32 (0: a beta outside [0, 1), or more than 2^22 steps)."""
+    return int(lib().tt_adam_coef_len(beta1, beta2))
+
+
+def adam_coef_tables(lr: float, beta1: float, beta2: float, length: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tt_adam_coef_fill: host float32 tensors (alpha [length], lr_t [length]), entry t-1 for step t."""
+    alpha = torch.empty(max(length, 0), dtype=torch.float32)
+    lr_t = torch.empty(max(length, 0), dtype=torch.float32)
+    check(lib().tt_adam_coef_fill(lr, beta1, beta2, length, alpha.data_ptr(), lr_t.data_ptr()))
+    return alpha, lr_t
+
+
+def _req_clock(clock: torch.Tensor) -> None:
+    _req(clock, "clock", torch.int64, 1)
+    if clock.numel() != 2 or not clock.is_contiguous():
+        raise ValueError("clock must be a contiguous int64 [2] tensor (the 16-byte tt_adam_clock)")
+
+
+def adam_clock_advance(clock: torch.Tensor, alpha_tab: torch.Tensor, lr_t_tab: torch.Tensor) -> None:
+    """tt_adam_clock_advance on the current stream: clock (int64 [2]: the step
+    word, then the float32 pair) moves one step along the device tables."""
+    _req_clock(clock)
+    for t, n in ((alpha_tab, "alpha_tab"), (lr_t_tab, "lr_t_tab")):
+        _req(t, n, torch.float32, 1)
+        if not t.is_contiguous() or t.numel() != alpha_tab.numel() or t.numel() < 1:
+            raise ValueError(f"{n} must be a contiguous, non-empty table of alpha_tab's length")
+    check(lib().tt_adam_clock_advance(clock.data_ptr(), alpha_tab.data_ptr(), lr_t_tab.data_ptr(),
+                                      alpha_tab.numel(), _stream()))
+
+
+def dense_adam_many_dev(jobs: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]], beta1: float,
+                        beta2: float, epsilon: float, clock: torch.Tensor) -> None:
+    """dense_adam on up to 8 (param, m, v, grad) buffers in one launch, the
+    step's coefficient read from `clock` on the device (tt_dense_adam_many_dev)."""
+    _req_clock(clock)
+    arr = (_native.DenseAdamJob * len(jobs))()
+    for i, (p, m, v, g) in enumerate(jobs):
+        for name, t in (("param", p), ("m", m), ("v", v), ("grad", g)):
+            _req(t, f"{name}[{i}]", torch.float32)
+            if not t.is_contiguous() or t.numel() != p.numel():
+                raise ValueError(f"dense_adam_many_dev: {name}[{i}] must be contiguous with param's size")
+        arr[i].param, arr[i].m, arr[i].v, arr[i].grad, arr[i].n = (p.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                                                   g.data_ptr(), p.numel())
+    check(lib().tt_dense_adam_many_dev(arr, len(jobs), beta1, beta2, epsilon, clock.data_ptr(), _stream()))
+
+
+def sparse_adam_dev(tables: Sequence[dict], batch: int, grad: Optional[torch.Tensor], beta1: float, beta2: float,
+                    epsilon: float, clock: torch.Tensor, ws_tag: str = "sparse") -> None:
+    """sparse_adam with the step's coefficient read from `clock` on the device
+    and the whole-table stages of all tables in one launch each
+    (tt_sparse_adam_dev).  grad may be None when every table brings its own
+    "grad" (one call for the tables of both towers, as sparse_adagrad)."""
+    _req_clock(clock)
+    ld = 0
+    if grad is not None:
+        _req(grad, "grad", torch.float32, 2)
+        ld = _row_major(grad, "grad")
+    elif any(t.get("grad") is None for t in tables):
+        raise ValueError("grad is None but some table has no per-table grad")
+    arr = _sparse_tables(tables, batch, adam=True)
+    L = lib()
+    need = L.tt_sparse_workspace_size(arr, len(tables), batch)
+    ws = Workspace.get(need, clock.device, ws_tag)
+    check(L.tt_sparse_adam_dev(arr, len(tables), batch, grad.data_ptr() if grad is not None else None, ld, beta1,
+                               beta2, epsilon, clock.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
 
 
 # --------------------------------------------------------------------------

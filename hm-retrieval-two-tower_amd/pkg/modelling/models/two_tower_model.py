@@ -685,7 +685,12 @@ class GraphedTrainStep:
     loss kernels and the optimizer kernels — with no Python or launch
     overhead.  Warm-up steps (run eagerly on a side stream before capture)
     are real optimisation steps on the example batch.  Requires an optimizer
-    whose kernels do not depend on the host step count (Adagrad)."""
+    whose kernels do not depend on the host step count: Adagrad, or Adam with
+    its step count moved to the device (Adam.enable_device_clock, called here
+    before the warm-up: the captured step starts with one launch that advances
+    the device's count and takes that step's two coefficients from a
+    host-filled table, so every replay is the next Adam step and
+    `optimizer.iterations` reports the device's count)."""
 
     def __init__(self, model: TwoTowerModel, example_batch: Optional[Dict[str, Any]], warmup: int = 2,
                  source=None):
@@ -693,10 +698,15 @@ class GraphedTrainStep:
         taken on the device inside the graph (tt_batch_take, cursor in device
         memory) — every replay then trains on the dataset's next batch and
         adds its loss to `loss_total` (fp64, device) with no host work."""
-        from pkg.modelling.optimizer_factory import Adagrad
+        from pkg.modelling.optimizer_factory import Adagrad, Adam
 
-        if not isinstance(model.optimizer, Adagrad):
-            raise ValueError("graph capture needs the Adagrad optimizer (Adam's coefficients depend on the step)")
+        if isinstance(model.optimizer, Adam):
+            # before the warm-up steps: they and the capture then take the same
+            # launches (ValueError for betas without a coefficient table)
+            model.optimizer.enable_device_clock(model.device)
+        elif not isinstance(model.optimizer, Adagrad):
+            raise ValueError("graph capture needs the Adagrad or the Adam optimizer "
+                             f"(got {type(model.optimizer).__name__})")
         self.model = model
         self.source = source
         if source is not None:

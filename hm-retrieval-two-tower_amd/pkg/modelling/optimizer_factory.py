@@ -10,6 +10,10 @@ Keras / TF kernels the reference reaches:
     dense  ResourceApplyAdam             -> tt_dense_adam
     sparse legacy _resource_apply_sparse (decays the WHOLE m/v slots, then a
            dense var update)              -> tt_sparse_adam
+    with the step count on the device (Adam.enable_device_clock, what a
+    captured step needs): tt_adam_clock_advance, then tt_dense_adam_many_dev
+    and tt_sparse_adam_dev, the same arithmetic with the step's coefficients
+    read from the device clock
 Slots are created on first use, as Keras creates them on the first
 apply_gradients.
 """
@@ -281,6 +285,103 @@ class Adam(_Optimizer):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported")
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+
+    # -- the step count: a host integer, or the device clock's word once enabled
+    _clock: Optional[torch.Tensor] = None
+
+    @property
+    def iterations(self) -> int:
+        """Steps applied so far.  With the device clock enabled this reads the
+        clock's step word (it synchronises the current stream), so it counts
+        eager steps and graph replays alike."""
+        if self._clock is not None:
+            return int(self._clock[0].item())
+        return self._iterations
+
+    @iterations.setter
+    def iterations(self, value: int) -> None:
+        self._iterations = int(value)
+        if self._clock is not None:
+            self._clock[:1].fill_(int(value))
+
+    def enable_device_clock(self, device) -> None:
+        """Move the step count into device memory (a tt_adam_clock), so a step
+        can be captured in a graph and every replay is the next step.
+
+        Builds, once, the table of both step coefficients from learning_rate,
+        beta_1 and beta_2 with the host function the host-step entries use
+        (tt_adam_coef_fill; the coefficients equal learning_rate from step
+        tt_adam_coef_len on, where the table ends), uploads it and sets the
+        clock's step to the current `iterations`.  learning_rate is read HERE:
+        a later change of the attribute does not reach the table.  From then on
+        every apply, eager or captured, is one adam_clock_advance, one
+        dense_adam_many_dev and the sparse_adam_dev calls, with results equal to
+        the host-step path's bit for bit, and the device word is the count
+        `iterations` reports.  A second call is a no-op.  Raises ValueError for
+        betas whose table cannot be built (beta = 1, or so close to 1 that it
+        would pass 2^22 entries)."""
+        if self._clock is not None:
+            return
+        length = hip_ops.adam_coef_len(self.beta_1, self.beta_2)
+        if length == 0:
+            raise ValueError(f"Adam's device step clock needs beta_1 and beta_2 in [0, 1) whose powers vanish in fp32 "
+                             f"within 2^22 steps; got beta_1={self.beta_1}, beta_2={self.beta_2}")
+        alpha, lr_t = hip_ops.adam_coef_tables(self.learning_rate, self.beta_1, self.beta_2, length)
+        device = torch.device(device)
+        self._coef_tables = (alpha.to(device), lr_t.to(device))
+        clock = torch.zeros(2, dtype=torch.int64, device=device)
+        clock[:1].fill_(self._iterations)
+        self._clock = clock
+
+    def apply_gradients(self, towers) -> None:
+        if self._clock is None:
+            return super().apply_gradients(towers)
+        self._apply_dev(towers)  # its first launch advances the device's count
+
+    minimize = apply_gradients
+
+    def _apply_dev(self, towers) -> None:
+        b1, b2, eps, clock = self.beta_1, self.beta_2, self.epsilon, self._clock
+        hip_ops.adam_clock_advance(clock, *self._coef_tables)
+        jobs = []
+        for tower in towers:
+            flat = tower.dense.flat
+            if flat.grad is not None:
+                m, v = self._slot(flat, 2, 0.0)
+                jobs.append((flat.data, m, v, flat.grad))
+        if jobs:  # both towers' MLP buffers in one launch
+            hip_ops.dense_adam_many_dev(jobs, b1, b2, eps, clock)
+        calls = []  # (specs, batch) per tower with an input gradient
+        for tower in towers:
+            layer = tower.input_layer
+            if layer.last_grad is None or not layer.embedding_layers:
+                continue
+            specs = []
+            for src in layer.sparse_sources():
+                t = src["table"]
+                m, v = self._slot(t.weight, 2, 0.0)
+                specs.append(dict(table=t.weight, slot0=m, slot1=v, ids=src["ids"],
+                                  grad_col_offset=src["grad_col_offset"], grad=layer.last_grad))
+            if specs:
+                calls.append((specs, layer.last_grad.shape[0]))
+        if len({batch for _, batch in calls}) == 1:
+            # every tower's tables in ONE call (each table reads its own tower's
+            # input gradient): one sort, one decay launch, one update launch
+            calls = [([s for specs, _ in calls for s in specs], calls[0][1])]
+        for specs, batch in calls:  # batches differ (mixed negatives: B and B + M rows): one call per tower
+            hip_ops.sparse_adam_dev(specs, batch, None, b1, b2, eps, clock)
+
+        def apply_group(group, batch):
+            bag_specs = []
+            for t, ids_flat, G in group:
+                m, v = self._slot(t.weight, 2, 0.0)
+                bag_specs.append(dict(table=t.weight, slot0=m, slot1=v, ids=[ids_flat], grad_col_offset=[0], grad=G))
+            hip_ops.sparse_adam_dev(bag_specs, batch, None, b1, b2, eps, clock, ws_tag=self.BAG_WS_TAG)
+
+        for tower in towers:
+            layer = tower.input_layer
+            if layer.last_grad is not None and layer.embedding_layers:
+                self._apply_bags(tower, layer.last_grad, apply_group)
 
     def _apply(self, towers) -> None:
         step = self.iterations + 1

@@ -394,6 +394,79 @@ int tt_dense_adam(float* param, float* m, float* v, const float* grad,
                   int64_t n, float lr, float beta1, float beta2, float epsilon,
                   int64_t step, tt_stream_t stream);
 
+/* Adam with the step count in device memory, for a captured train step.
+ *
+ * Adam depends on the step t only through two fp32 coefficients, which
+ * tt_dense_adam and tt_sparse_adam compute on the host with powf:
+ *   alpha = (lr * sqrt(1 - beta2^t)) / (1 - beta1^t)      (dense, TF ApplyAdamOp)
+ *   lr_t  = lr * (sqrt(1 - beta2^t) / (1 - beta1^t))      (sparse, legacy Keras)
+ * The device's powf is not the host's, so the _dev entries below never compute
+ * them: the host fills a table of both, one entry per step, with the same
+ * function the two entries above use, and a one-thread launch moves a device
+ * clock one step along it.  The table is finite because the coefficients
+ * saturate: once beta^t <= 2^-25, 1 - beta^t == 1 in fp32 and both equal lr
+ * for every later step (the host's powers are monotone in t over the 2^22 steps
+ * a table may hold), so the clock clamps its index at the table's last entry.
+ *
+ * tt_adam_coef_len: L, the first step at which 1 - beta^t == 1 for both betas
+ * as that host function evaluates them (found by evaluating it step by step,
+ * not from a formula: the fp32 value of beta moves L); from step L on both
+ * coefficients are lr.  0 when a beta is outside [0, 1) (NaN included) or L
+ * would exceed 2^22.  beta1 = beta2 = 0 gives 1.  (0.9, 0.999) gives 17321.
+ * tt_adam_coef_fill: HOST arrays alpha[len], lr_t[len]; entry t-1 holds step
+ * t's pair, bit for bit what tt_dense_adam / tt_sparse_adam use at `step` = t.
+ * TT_ERR_BAD_ARG for a non-finite lr, a beta outside [0, 1), len < 1 or NULL. */
+int64_t tt_adam_coef_len(float beta1, float beta2);
+int tt_adam_coef_fill(float lr, float beta1, float beta2, int64_t len, float* alpha, float* lr_t);
+
+/* The device clock: 16 bytes of device memory, 8-byte aligned.
+ *   offset 0  int64  step   steps taken so far (the last advance made it step t)
+ *   offset 8  float  alpha  step t's dense coefficient
+ *   offset 12 float  lr_t   step t's sparse coefficient
+ * The host sets `step` (e.g. to the optimizer's iteration count) before the
+ * first advance; alpha / lr_t are valid after it. */
+typedef struct {
+  int64_t step;
+  float alpha;
+  float lr_t;
+} tt_adam_clock;
+
+/* One launch of one thread, plain stores: step += 1, then (alpha, lr_t) =
+ * entry min(step, len) - 1 of the DEVICE copies of the filled tables (entry 0
+ * for a step below 1).  It synchronises with nothing and can be captured:
+ * every replay advances the clock, as tt_mixed_candidates' step word does.
+ * Kernels ordered after it on the stream read the new pair. */
+int tt_adam_clock_advance(tt_adam_clock* clock, const float* alpha_tab, const float* lr_t_tab,
+                          int64_t len, tt_stream_t stream);
+
+/* tt_dense_adam on up to 8 buffers in ONE launch (a grid-stride loop over
+ * their concatenation), alpha read from *clock on the device: bit-identical
+ * to one tt_dense_adam per buffer at step clock->step with the lr the table
+ * was filled for.  n may be 0 (pointers then unused). */
+typedef struct {
+  float* param;
+  float* m;
+  float* v;
+  const float* grad;
+  int64_t n;
+} tt_dense_adam_job;
+int tt_dense_adam_many_dev(const tt_dense_adam_job* jobs, int32_t num_jobs, float beta1, float beta2,
+                           float epsilon, const tt_adam_clock* clock, tt_stream_t stream);
+
+/* tt_sparse_adam with lr_t read from *clock on the device: the same three
+ * stages in the same order (whole slots decayed, tt_sparse_adam's scatter,
+ * whole tables updated), bit-identical to it at step clock->step.  The decay
+ * of ALL tables is one launch and so is the update (16 tables a launch; 16-byte
+ * accesses for a table whose three buffers are 16-byte aligned), where
+ * tt_sparse_adam takes one of each per table.  Same validation, workspace
+ * (tt_sparse_workspace_size) and fingerprint checks; batch == 0 still decays
+ * and updates. */
+int tt_sparse_adam_dev(const tt_sparse_table* tables, int32_t num_tables,
+                       int64_t batch, const float* grad, int64_t grad_stride,
+                       float beta1, float beta2, float epsilon,
+                       const tt_adam_clock* clock, void* workspace,
+                       size_t workspace_bytes, tt_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * K5+K6+K7  Fused in-batch scores, logQ correction and softmax
  * cross-entropy (reduction SUM) with its gradient.
