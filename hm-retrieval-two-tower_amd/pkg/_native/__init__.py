@@ -28,6 +28,8 @@ __all__ = [
     "L2NormGradJob",
     "BagJob",
     "BagGradJob",
+    "ClipRegion",
+    "MAX_CLIP_REGIONS",
     "MAX_BAG_JOBS",
     "BAG_POOLINGS",
     "MAX_SEGMENTS",
@@ -204,6 +206,20 @@ class BagGradJob(ctypes.Structure):
         ("scale", c_void_p),
         ("ids_flat", c_void_p),
         ("grad", c_void_p),
+    ]
+
+
+MAX_CLIP_REGIONS = 32  # TT_CLIP_MAX_REGIONS: regions per launch (any number is taken, in chunks)
+
+
+class ClipRegion(ctypes.Structure):
+    _fields_ = [
+        ("g", c_void_p),
+        ("rows", c_int64),
+        ("cols", c_int32),
+        ("ld", c_int64),
+        ("row_ids", c_void_p),
+        ("var", c_int32),
     ]
 
 
@@ -503,6 +519,11 @@ _PROTOS = {
     "tt_bag_grad_expand": (c_int32, [POINTER(BagGradJob), c_int32, c_int64, c_void_p]),
     "tt_inbatch_weight_rows": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_int32, c_void_p]),
+    "tt_grad_clip_workspace_size": (c_size_t, [POINTER(ClipRegion), c_int32]),
+    "tt_grad_sumsq": (c_int32, [POINTER(ClipRegion), c_int32, c_int32, c_float, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "tt_grad_clip_apply": (c_int32, [POINTER(ClipRegion), c_int32, c_int32, c_float, c_float, c_float, c_void_p,
+                                     c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

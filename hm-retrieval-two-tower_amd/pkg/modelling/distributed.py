@@ -926,6 +926,9 @@ class ShardedTrainStep:
         opt = model.optimizer
         if not isinstance(opt, Adagrad):
             raise NotImplementedError("ShardedTrainStep supports the Adagrad optimizer")
+        if getattr(opt, "clips", False):
+            raise NotImplementedError("ShardedTrainStep does not support gradient clipping (clipvalue / clipnorm / "
+                                      "global_clipnorm); train single-device")
         self.model = model
         self.group = group
         self.ops = ops or EmbeddingOps.hip()

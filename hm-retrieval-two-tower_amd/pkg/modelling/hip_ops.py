@@ -47,6 +47,9 @@ __all__ = [
     "l2norm_rows_grad",
     "gather_bag",
     "bag_grad_expand",
+    "clip_regions",
+    "grad_sumsq",
+    "grad_clip_apply",
     "probe_arm",
     "probe_arm_repeat",
     "route_requests",
@@ -1856,3 +1859,88 @@ def bag_grad_expand(jobs: Sequence[tuple], batch: int) -> None:
         q.dout, q.dout_stride, q.scale = dout.data_ptr(), ld, scale.data_ptr()
         q.ids_flat, q.grad = ids_flat.data_ptr(), grad.data_ptr()
     check(lib().tt_bag_grad_expand(arr, len(jobs), batch, _stream()))
+
+
+# --------------------------------------------------------------------------
+# Gradient clipping: clipvalue / clipnorm / global_clipnorm in place
+# --------------------------------------------------------------------------
+class ClipRegions(tuple):
+    """clip_regions' result: (tt_clip_region array, count, device)."""
+
+
+def clip_regions(regions: Sequence[tuple], num_vars: int) -> ClipRegions:
+    """The tt_clip_region array of `regions`, each (g, row_ids, var): g a 1-D
+    fp32 tensor with unit stride (one row) or a 2-D view with unit column
+    stride and any row stride >= its width (a column range of a wider
+    matrix); row_ids None or a contiguous [rows] int32 tensor (rows with id <
+    0 are skipped); var in [0, num_vars).  An empty g is a region without
+    values."""
+    arr = (_native.ClipRegion * max(len(regions), 1))()
+    dev = None
+    for i, (g, row_ids, var) in enumerate(regions):
+        _req(g, f"g[{i}]", torch.float32)
+        if dev is not None and g.device != dev:
+            raise ValueError(f"g[{i}] must live on {dev} (got {g.device})")
+        dev = g.device
+        if g.dim() == 1:
+            if g.numel() > 1 and g.stride(0) != 1:
+                raise ValueError(f"g[{i}] must have unit stride")
+            rows, cols, ld = 1, g.numel(), g.numel()
+        elif g.dim() == 2:
+            rows, cols = g.shape
+            ld = _norm_ld(g, f"g[{i}]")
+        else:
+            raise ValueError(f"g[{i}] must be 1-D or 2-D, got shape {tuple(g.shape)}")
+        if cols >= 1 << 31:
+            raise ValueError(f"g[{i}]: {cols} columns do not fit an int32")
+        if not 0 <= int(var) < num_vars:
+            raise ValueError(f"region {i}: var={var} outside [0, {num_vars})")
+        q = arr[i]
+        q.g, q.rows, q.cols, q.ld, q.var = g.data_ptr(), rows, cols, ld, int(var)
+        q.row_ids = None
+        if row_ids is not None:
+            _req(row_ids, f"row_ids[{i}]", torch.int32, 1)
+            if row_ids.numel() != rows or not row_ids.is_contiguous() or row_ids.device != g.device:
+                raise ValueError(f"row_ids[{i}] must be a contiguous [{rows}] int32 tensor on {g.device}")
+            q.row_ids = row_ids.data_ptr()
+    return ClipRegions((arr, len(regions), dev))
+
+
+def _clip_out(t: torch.Tensor, name: str, dtype: torch.dtype, num_vars: int, dev) -> None:
+    _req(t, name, dtype, 1)
+    if t.numel() != num_vars or not t.is_contiguous() or (dev is not None and t.device != dev):
+        raise ValueError(f"{name} must be a contiguous [{num_vars}] {dtype} tensor on the gradients' device")
+
+
+def grad_sumsq(regions, num_vars: int, clipvalue: Optional[float], sumsq: torch.Tensor,
+               ws_tag: str = "grad_clip") -> None:
+    """sumsq[v] (fp64, [num_vars]) = the sum of squares of variable v's values
+    after the clipvalue clamp (None: no clamp), tt_grad_sumsq: fp64 from exact
+    products in a fixed order.  `regions`: clip_regions' input or its result."""
+    arr, n, dev = regions if isinstance(regions, ClipRegions) else clip_regions(regions, num_vars)
+    _clip_out(sumsq, "sumsq", torch.float64, num_vars, dev)
+    need = lib().tt_grad_clip_workspace_size(arr, n)
+    if need == 0:
+        raise ValueError("grad_sumsq: a region is too large")
+    ws = Workspace.get(need, sumsq.device, ws_tag)
+    check(lib().tt_grad_sumsq(arr, n, num_vars, float(clipvalue or 0.0), sumsq.data_ptr(), ws.data_ptr(),
+                              ws.numel(), _stream()))
+
+
+def grad_clip_apply(regions, num_vars: int, clipvalue: Optional[float], clipnorm: Optional[float],
+                    global_clipnorm: Optional[float], sumsq: Optional[torch.Tensor],
+                    factor: Optional[torch.Tensor]) -> None:
+    """g <- clamp(g, +-clipvalue) * f in place over every region
+    (tt_grad_clip_apply), f = c / max(fp32(sqrt(ss)), c) from sumsq per
+    variable (clipnorm) or over all variables (global_clipnorm), 1 with
+    neither; factor[v] (fp32, [num_vars]) receives f when given."""
+    arr, n, dev = regions if isinstance(regions, ClipRegions) else clip_regions(regions, num_vars)
+    if sumsq is not None:
+        _clip_out(sumsq, "sumsq", torch.float64, num_vars, dev)
+    elif clipnorm or global_clipnorm:
+        raise ValueError("grad_clip_apply: a norm needs sumsq")
+    if factor is not None:
+        _clip_out(factor, "factor", torch.float32, num_vars, dev)
+    check(lib().tt_grad_clip_apply(arr, n, num_vars, float(clipvalue or 0.0), float(clipnorm or 0.0),
+                                   float(global_clipnorm or 0.0), sumsq.data_ptr() if sumsq is not None else None,
+                                   factor.data_ptr() if factor is not None else None, _stream()))

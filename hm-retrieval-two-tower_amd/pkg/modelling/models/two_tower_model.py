@@ -452,10 +452,17 @@ class TwoTowerModel(AbstractKerasModel):
                 raise TypeError("loss must be pkg.modelling.losses.CategoricalCrossentropy(from_logits=True, ...)")
             self.loss = loss
         if optimizer is not None:
+            self._check_clipping(optimizer)
             self.optimizer = optimizer
             # a cached fit graph holds the old optimizer's slot addresses
             self._device_fit_graph = None
         self._warn_mixed_hits()
+
+    def _check_clipping(self, optimizer) -> None:
+        if self.fused_optimizer_apply and getattr(optimizer, "clips", False):
+            raise ValueError("fused_optimizer_apply applies each tower's update inside the backward; gradient "
+                             "clipping (clipvalue / clipnorm / global_clipnorm) needs every gradient before any "
+                             "update: use one or the other")
 
     def check_optimizer_status(self) -> None:
         """Raise if a sparse apply since the last check refused stale or
@@ -476,8 +483,12 @@ class TwoTowerModel(AbstractKerasModel):
 
         if self.optimizer is None:
             raise RuntimeError("call compile(optimizer=...) before training")
+        # a clipping optimizer needs every gradient before any update: no
+        # update from inside the backward, apply_gradients after it
+        clips = bool(getattr(self.optimizer, "clips", False))
+        self._check_clipping(self.optimizer)
         fused = self.fused_optimizer_apply and isinstance(self.optimizer, Adagrad) and self.device.type == "cuda"
-        dense_early = (not fused and DENSE_EARLY and isinstance(self.optimizer, Adagrad)
+        dense_early = (not fused and not clips and DENSE_EARLY and isinstance(self.optimizer, Adagrad)
                        and self.device.type == "cuda")
         self._dense_done = set()
         self._sparse_done = set()

@@ -16,11 +16,16 @@ Keras / TF kernels the reference reaches:
     read from the device clock
 Slots are created on first use, as Keras creates them on the first
 apply_gradients.
+Both take the legacy keywords clipvalue, clipnorm and global_clipnorm
+(_transform_gradients: clamp, then a per-variable or a global norm bound),
+applied in place on the device before any update: _Optimizer.clip_gradients ->
+tt_grad_sumsq, tt_grad_clip_apply.  decay is refused.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 import logging
+import math
 
 import torch
 
@@ -28,7 +33,62 @@ from pkg.modelling import hip_ops
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["OptimizerFactory", "Adagrad", "Adam"]
+__all__ = ["OptimizerFactory", "Adagrad", "Adam", "plan_clip_regions", "clip_tower_desc"]
+
+
+CLIP_KEYS = ("clipvalue", "clipnorm", "global_clipnorm")
+
+
+def plan_clip_regions(towers: Sequence[dict]) -> Tuple[List[str], List[dict]]:
+    """The variables Keras clips as one tensor each, and where their gradient
+    values lie.  Pure Python (no tensor is touched).  Each tower is a dict:
+      name      prefix of its variables' names
+      layout    DenseStack.layout, [(w_off, fan_in, fan_out, b_off)]; [] when
+                the tower has no dense gradient this step
+      rows      rows of its input gradient (B, or B + M for the candidate
+                tower under mixed negatives); None when it has none
+      features  its categorical lookups in call order, (table name, dim,
+                column offset, L): L None for a one-id lookup, the sequence
+                length for a sequence feature
+    Variables, in order, per tower: every Dense layer's kernel then bias, then
+    every embedding table at its first lookup (a name looked up twice is ONE
+    variable with several regions).  Numeric columns belong to no variable.
+    Returns (names, regions); a region is a dict with var, tower and
+      kind "dense": start, size      flat.grad[start : start + size]
+      kind "input": col, cols, rows  last_grad[:, col : col + cols]
+      kind "bag":   bag, cols, rows  the expanded G of the tower's bag-th
+                                     sequence feature, rows of valid slots only"""
+    names: List[str] = []
+    regions: List[dict] = []
+    for ti, t in enumerate(towers):
+        for li, (w_off, fi, fo, b_off) in enumerate(t["layout"]):
+            for what, start, size in (("kernel", w_off, fi * fo), ("bias", b_off, fo)):
+                regions.append(dict(var=len(names), tower=ti, kind="dense", start=start, size=size))
+                names.append(f"{t['name']}/dense_{li}/{what}")
+        var_of: Dict[str, int] = {}
+        bag = 0
+        for table, dim, col, L in t["features"]:
+            if table not in var_of:
+                var_of[table] = len(names)
+                names.append(f"{t['name']}/embedding/{table}")
+            rows = t["rows"]
+            if L is None:
+                if rows is not None:
+                    regions.append(dict(var=var_of[table], tower=ti, kind="input", col=col, cols=dim, rows=rows))
+            else:
+                if rows is not None:
+                    regions.append(dict(var=var_of[table], tower=ti, kind="bag", bag=bag, cols=dim, rows=rows * L))
+                bag += 1
+    return names, regions
+
+
+def clip_tower_desc(tower, name: str, rows: Optional[int], dense: bool = True) -> dict:
+    """plan_clip_regions' description of a Tower (its structure; `rows` and
+    `dense` say which gradients this step has)."""
+    layer = tower.input_layer
+    features = [(f.name, layer.embedding_layers[f.name].dim, off, f.sequence_length if f.is_sequence else None)
+                for f, off in zip(layer.categorical_features, layer.column_offsets())]
+    return dict(name=name, layout=list(tower.dense.layout) if dense else [], rows=rows, features=features)
 
 
 class _Optimizer:
@@ -37,12 +97,100 @@ class _Optimizer:
         self.name = name
         self.iterations = 0
         self._slots: Dict[int, List[torch.Tensor]] = {}
-        if kwargs:
-            unknown = set(kwargs) - {"clipnorm", "clipvalue", "global_clipnorm", "decay"}
-            if unknown:
-                raise TypeError(f"Unexpected keyword argument(s) passed to optimizer: {sorted(unknown)}")
-            if any(kwargs.get(k) for k in ("clipnorm", "clipvalue", "global_clipnorm", "decay")):
-                raise NotImplementedError("gradient clipping / decay are not supported")
+        unknown = set(kwargs) - set(CLIP_KEYS) - {"decay"}
+        if unknown:
+            raise TypeError(f"Unexpected keyword argument(s) passed to optimizer: {sorted(unknown)}")
+        if kwargs.get("decay"):
+            raise NotImplementedError("decay is not supported")
+        for k in CLIP_KEYS:
+            v = kwargs.get(k)
+            if v is not None:
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+                    raise ValueError(f"{k} must be None or a positive finite number, got {v!r}")
+                v = float(v)
+            setattr(self, k, v)
+        if self.clipnorm is not None and self.global_clipnorm is not None:
+            raise ValueError("Cannot accept both `clipnorm` and `global_clipnorm`, "
+                             f"got clipnorm={self.clipnorm}, global_clipnorm={self.global_clipnorm}")
+        self.clips = any(getattr(self, k) is not None for k in CLIP_KEYS)
+        self.clip_variable_names: List[str] = []
+        self._clip_state = None  # (num_vars, device, sumsq fp64, factor fp32): persistent, a captured step replays into them
+        self._clip_bags: Dict[int, list] = {}
+
+    # -- gradient clipping (clipvalue, clipnorm, global_clipnorm) --------------
+    TOWER_NAMES = ("query", "candidate")
+
+    @property
+    def last_clip_sumsq(self) -> Optional[torch.Tensor]:
+        """Per variable (clip_variable_names), the fp64 sum of squares of its
+        gradient values after clipvalue, of the last clip_gradients; None
+        before the first one and with neither norm set.  A device tensor:
+        reading it is the caller's synchronisation."""
+        if self._clip_state is None or (self.clipnorm is None and self.global_clipnorm is None):
+            return None
+        return self._clip_state[2]
+
+    @property
+    def last_clip_factors(self) -> Optional[torch.Tensor]:
+        """Per variable, the fp32 factor the last clip_gradients applied (1
+        where the norm did not exceed its bound; one value for all under
+        global_clipnorm)."""
+        return None if self._clip_state is None else self._clip_state[3]
+
+    def clip_gradients(self, towers) -> None:
+        """Keras' _transform_gradients on the device, in place, before any
+        update: clipvalue, then clipnorm per variable or global_clipnorm over
+        all (plan_clip_regions says what a variable is).  Sequence features'
+        gradients are expanded here, clipped as the rows the bag applies
+        consume, and handed to them (_apply_bags).  Launches on the current
+        stream, no host read; nothing is launched without a clipping keyword."""
+        if not self.clips:
+            return
+        names, regions = self._clip_regions(towers)
+        if not regions:
+            return
+        device = regions[0][0].device
+        st = self._clip_state
+        if st is None or st[0] != len(names) or st[1] != device:
+            st = self._clip_state = (len(names), device, torch.zeros(len(names), dtype=torch.float64, device=device),
+                                     torch.ones(len(names), dtype=torch.float32, device=device))
+        self.clip_variable_names = names
+        arr = hip_ops.clip_regions(regions, len(names))
+        norm = self.clipnorm is not None or self.global_clipnorm is not None
+        if norm:
+            hip_ops.grad_sumsq(arr, len(names), self.clipvalue, st[2])
+        hip_ops.grad_clip_apply(arr, len(names), self.clipvalue, self.clipnorm, self.global_clipnorm,
+                                st[2] if norm else None, st[3])
+
+    def _clip_regions(self, towers) -> Tuple[List[str], List[tuple]]:
+        """plan_clip_regions for this step's gradients, bound to their tensors:
+        (variable names, [(g, row_ids or None, var)] for hip_ops.clip_regions).
+        Expands the towers' bag gradients (kept for _apply_bags)."""
+        descs, expanded = [], []
+        self._clip_bags = {}
+        for ti, tower in enumerate(towers):
+            layer, g = tower.input_layer, tower.input_layer.last_grad
+            bags = []
+            if g is not None and layer.bag_sources():
+                # one buffer per tower: every tower's G is alive until the norm is known
+                bags = self._expand_bags(tower, g, tag=f"bag_grad_clip{ti}")
+                self._clip_bags[id(tower)] = bags
+            expanded.append(bags)
+            name = self.TOWER_NAMES[ti] if len(towers) == len(self.TOWER_NAMES) else f"tower{ti}"
+            descs.append(clip_tower_desc(tower, name, None if g is None else g.shape[0],
+                                         dense=tower.dense.flat.grad is not None))
+        names, plan = plan_clip_regions(descs)
+        regions = []
+        for r in plan:
+            tower = towers[r["tower"]]
+            if r["kind"] == "dense":
+                regions.append((tower.dense.flat.grad[r["start"]:r["start"] + r["size"]], None, r["var"]))
+            elif r["kind"] == "input":
+                regions.append((tower.input_layer.last_grad[:, r["col"]:r["col"] + r["cols"]], None, r["var"]))
+            else:
+                _, _, ids_flat, G = expanded[r["tower"]][r["bag"]]
+                regions.append((G, ids_flat, r["var"]))
+        return names, regions
 
     def _slot(self, param: torch.Tensor, n: int, init: float) -> List[torch.Tensor]:
         key = id(param)
@@ -62,16 +210,11 @@ class _Optimizer:
     # -- sequence features: a tower's bag tables as flat sparse problems -------
     BAG_WS_TAG = "sparse_bag"  # the regular tables' presorted keys may sit in "sparse"
 
-    def _apply_bags(self, tower, grad: Optional[torch.Tensor], apply) -> None:
-        """Expand the tower's input gradient into one gradient row per lookup of
-        its sequence features (ONE tt_bag_grad_expand launch per 8 features) and
-        hand every group of equal L to `apply(specs, batch * L, G)` as a flat
-        problem: one source per table, ids_flat, grad_ld = dim, column 0.  On
-        the current stream and workspace scope, after the tower's regular
-        sparse call; nothing is launched without a sequence feature."""
+    def _expand_bags(self, tower, grad: torch.Tensor, tag: str = "bag_grad") -> list:
+        """One gradient row per lookup of the tower's sequence features (ONE
+        tt_bag_grad_expand launch per 8 features), carved from the workspace
+        `tag`: [(L, table, ids_flat [B * L], G [B * L, dim])] per feature."""
         bags = tower.input_layer.bag_sources()
-        if not bags or grad is None:
-            return
         if grad.stride(1) != 1:
             grad = grad.contiguous()
         B = grad.shape[0]
@@ -80,18 +223,36 @@ class _Optimizer:
         for n, dim in sizes:  # 256-byte aligned carves: ids_flat then G per feature
             offs.append((total, total + (n * 4 + 255) // 256 * 256))
             total = offs[-1][1] + (n * dim * 4 + 255) // 256 * 256
-        buf = hip_ops.Workspace.get(total, grad.device, "bag_grad")
-        jobs, by_len = [], {}
+        buf = hip_ops.Workspace.get(total, grad.device, tag)
+        jobs, out = [], []
         for b, (n, dim), (o_ids, o_g) in zip(bags, sizes, offs):
             ids_flat = buf[o_ids:o_ids + n * 4].view(torch.int32)
             G = buf[o_g:o_g + n * dim * 4].view(torch.float32).view(n, dim)
             t = b["table"]
             jobs.append((t.num_rows, b["ids"], b["pooling"], grad, b["grad_col_offset"], b["scale"], ids_flat, G))
-            by_len.setdefault(b["ids"].shape[1], []).append((t, ids_flat, G))
+            out.append((b["ids"].shape[1], t, ids_flat, G))
         for i in range(0, len(jobs), hip_ops._native.MAX_BAG_JOBS):
             hip_ops.bag_grad_expand(jobs[i:i + hip_ops._native.MAX_BAG_JOBS], B)
-        for L, group in by_len.items():  # tables of different L take separate calls
-            apply(group, B * L)
+        return out
+
+    def _apply_bags(self, tower, grad: Optional[torch.Tensor], apply) -> None:
+        """Expand the tower's input gradient into one gradient row per lookup of
+        its sequence features (ONE tt_bag_grad_expand launch per 8 features) and
+        hand every group of equal L to `apply(specs, batch * L, G)` as a flat
+        problem: one source per table, ids_flat, grad_ld = dim, column 0.  On
+        the current stream and workspace scope, after the tower's regular
+        sparse call; nothing is launched without a sequence feature.  After
+        clip_gradients the rows it expanded (and clipped) are applied instead."""
+        expanded = self._clip_bags.pop(id(tower), None)
+        if expanded is None:
+            if not tower.input_layer.bag_sources() or grad is None:
+                return
+            expanded = self._expand_bags(tower, grad)
+        by_len = {}
+        for L, t, ids_flat, G in expanded:
+            by_len.setdefault(L, []).append((t, ids_flat, G))
+        for group in by_len.values():  # tables of different L take separate calls
+            apply(group, group[0][1].numel())
 
 
 class Adagrad(_Optimizer):
@@ -236,6 +397,7 @@ class Adagrad(_Optimizer):
 
     def _apply(self, towers) -> None:
         lr, eps, init = self.learning_rate, self.epsilon, self.initial_accumulator_value
+        self.clip_gradients(towers)
         for tower in towers:
             flat = tower.dense.flat
             if flat.grad is not None:
@@ -342,6 +504,7 @@ class Adam(_Optimizer):
 
     def _apply_dev(self, towers) -> None:
         b1, b2, eps, clock = self.beta_1, self.beta_2, self.epsilon, self._clock
+        self.clip_gradients(towers)
         hip_ops.adam_clock_advance(clock, *self._coef_tables)
         jobs = []
         for tower in towers:
@@ -386,6 +549,7 @@ class Adam(_Optimizer):
     def _apply(self, towers) -> None:
         step = self.iterations + 1
         lr, b1, b2, eps = self.learning_rate, self.beta_1, self.beta_2, self.epsilon
+        self.clip_gradients(towers)
         for tower in towers:
             flat = tower.dense.flat
             if flat.grad is not None:

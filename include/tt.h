@@ -1249,6 +1249,59 @@ int tt_inbatch_weight_rows(const float* w, const float* lse, const float* row_lo
                            float* lse_w, float* row_loss_w, float* wloss,
                            float* dq, int64_t lddq, int32_t dim, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Gradient clipping (tf.keras.optimizers.legacy clipvalue / clipnorm /
+ * global_clipnorm, in the order of _transform_gradients), in place over the
+ * gradient values the optimizer entries consume, entirely on the device.
+ *
+ * A region is a [rows, cols] range of fp32 (row r at g + r * ld; any column
+ * offset, any ld >= cols) that belongs to variable `var`; several regions may
+ * share a variable (a table looked up by several features).  With row_ids,
+ * row r is skipped (neither read nor written) when row_ids[r] < 0: the rows
+ * tt_bag_grad_expand leaves unwritten.  Regions reach the kernels by value,
+ * TT_CLIP_MAX_REGIONS per launch; any number is taken, in chunks.
+ *
+ * tt_grad_sumsq: sumsq[v] = sum over variable v's values of c(g)^2 with
+ *   c(g) = min(max(g, -clipvalue), clipvalue) (clipvalue <= 0: c(g) = g).
+ *   Accumulated in fp64 from the exact products in a fixed order (per thread,
+ *   a fixed tree per workgroup into the workspace, then one workgroup per
+ *   variable over its partials; region chunks of one call add in call order):
+ *   no floating-point atomics, equal bits every run, and equal bits for the
+ *   same values at another address or leading dimension (16-byte accesses are
+ *   used only where base and ld allow them, with the same element -> thread
+ *   map).  A variable with no value gets 0.  Launches: 2 per region chunk.
+ * tt_grad_clip_apply: g <- c(g) * f per element (one fp32 multiply), with
+ *   f = 1                                   (neither norm set),
+ *   f = clipnorm / max(n_v, clipnorm),  n_v = fp32(sqrt(sumsq[var]))  or
+ *   f = global_clipnorm / max(n, global_clipnorm),  n = fp32(sqrt(sumsq[0] +
+ *   sumsq[1] + ... in index order)): one IEEE fp32 division, exactly 1.0f for
+ *   n <= c (an all-zero gradient included), so a clip that does not trigger
+ *   changes no bit; a NaN norm gives a NaN factor.  factor[var] = f when
+ *   factor is not NULL.  With neither norm set sumsq may be NULL.  Setting
+ *   both norms is an error, as in Keras.  Launches: 1 per region chunk.
+ * Stream-ordered; no allocation, no host read, no host-to-device copy.
+ * TT_ERR_BAD_ARG (checked on the host before any launch): NULL regions with
+ * num_regions > 0, num_regions < 0, num_vars < 1, var outside [0, num_vars),
+ * negative rows or cols, ld < cols with rows > 1, a NULL g with values, NULL
+ * sumsq where it is read, a NULL workspace, a NaN setting.  A workspace below
+ * tt_grad_clip_workspace_size: TT_ERR_WORKSPACE.  A region of 2^31 or more
+ * 4-float chunks: TT_ERR_UNSUPPORTED. */
+#define TT_CLIP_MAX_REGIONS 32
+typedef struct {
+  float* g;
+  int64_t rows;
+  int32_t cols;
+  int64_t ld;
+  const int32_t* row_ids;  /* NULL, or [rows]: rows with id < 0 are skipped */
+  int32_t var;
+} tt_clip_region;
+size_t tt_grad_clip_workspace_size(const tt_clip_region* regions, int32_t num_regions);
+int tt_grad_sumsq(const tt_clip_region* regions, int32_t num_regions, int32_t num_vars, float clipvalue,
+                  double* sumsq, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_grad_clip_apply(const tt_clip_region* regions, int32_t num_regions, int32_t num_vars, float clipvalue,
+                       float clipnorm, float global_clipnorm, const double* sumsq, float* factor,
+                       tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
