@@ -572,7 +572,7 @@ def route_fixed(lookups: Sequence[Tuple[torch.Tensor, int, int]], world: int, nu
                 overflow: Optional[torch.Tensor] = None, ordered: bool = False, owner: bool = False,
                 idx_out: Optional[torch.Tensor] = None):
     """The fixed-capacity route in one call (tt_route_fixed; one launch for
-    <= 16384 lookups): (send_padded [world*cap, 2], idx_padded [L, B],
+    <= 8192 lookups, kRsMax, whose keys fit 32 bits): (send_padded [world*cap, 2], idx_padded [L, B],
     counts [world] int64, (order, grp_first, grp_last) if ordered, and at
     world 1 with owner=True (tags, rows, table_ids [num_tags, cap]) of the
     slots) — equal to route_requests + route_pad (+ route_owner).  idx_out:

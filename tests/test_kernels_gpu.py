@@ -1009,7 +1009,7 @@ def test_sparse_routed_adagrad_world1_equals_sparse_adagrad(cuda, B, small):
 
 @pytest.mark.parametrize("world,B", [(1, 2048), (3, 2048), (8, 1024), (1, 16384), (2, 16384)])
 def test_route_fixed_equals_composed_route(cuda, world, B):
-    """tt_route_fixed (one workgroup for <= 16384 lookups; the multi-launch
+    """tt_route_fixed (one workgroup for <= 8192 lookups, kRsMax; the multi-launch
     path above that) equals tt_route_requests_ordered + tt_route_pad (+
     tt_route_owner at world 1) on every output, bit for bit: padded requests,
     slots, counts, sorted order, group bounds and the owner view — Zipf ids
