@@ -1207,9 +1207,9 @@ int pick_dpad(int dim) {
 }
 
 // Splits of the streamed extent so that the grid has >= 512 workgroups: two
-// rounds over the 256 CUs (the pass holds 426 registers per lane, so one
-// workgroup per CU).  At the C3 batch (B = 16384, 128 stationary blocks)
-// S = 4 beat S = 2 — one round, fewer split partials — by 19-24 us per train
+// per CU (the plain pass compiles to 232 registers per lane, which allows
+// two waves per SIMD: two workgroups per CU).  At the C3 batch (B = 16384,
+// 128 stationary blocks) S = 4 beat S = 2 — one round, fewer split partials — by 19-24 us per train
 // step (same box, 3 interleaved pairs; rows pass 116 vs 129 us, cols 104 vs
 // 118 us: the second round evens out the workgroups' finishing times).
 // TT_INBATCH_WGS overrides the target.

@@ -27,12 +27,18 @@
 // two stages it asks for past the last are offset past the descriptor's range
 // and cost no traffic (fetch_a).
 // 4 waves; wave w computes rows 0..63 x the 32-column blocks w, w+4, w+8
-// (each B fragment is loaded by exactly one wave of the workgroup).
+// (each B fragment is loaded by exactly one wave of the workgroup); a block
+// that lies wholly past N is skipped by its wave, and an unmasked width whose
+// last 128-column unit has one real block (N = 258) runs in a slim width
+// class with a 73 KiB tile and under 256 registers, two workgroups per CU
+// (mlp_rows_block has both).
 // Epilogue: the operands that do not depend on the accumulators are in flight
 // before they are needed — the bias before the main loop, a thread's whole
 // share of the epilogue mask (8 NCB 16-B loads) before the accumulators go
 // through LDS — and the stores are 8 NCB unrolled trips of range-checked
 // buffer stores: no per-trip division, branch or wait on the previous store.
+// The LDS tile's pitch is the workgroup's own columns (n4 + 4), not the
+// 128 NCB its blocks span.
 //
 // N > 384 (a workgroup keeps at most 3 blocks per wave = 384 columns in
 // accumulators and a 97 KiB output tile): the launch covers (row blocks) x
@@ -135,23 +141,57 @@ __device__ __forceinline__ int a_lds_off(int plane, int row, int chunk) {
 }
 
 // A stages (2 x 2 planes x 64 rows x 128 B = 32 KiB), then the output tile
-// [64][NCB * 128 + 4] fp32 of the epilogue (<= 97 KiB)
-template <int NCB>
+// [64][n4 + 4] fp32 of the epilogue, n4 = the workgroup's own columns rounded
+// up to 4 (not the NCB * 128 its waves' blocks span).  Two compile-time width
+// classes size it: the full one holds any n4 <= COLS = 128 NCB (<= 97 KiB);
+// SLIM holds the widths whose last 128-column unit has real columns in its
+// first 32-column block only, n4 <= COLS = 128 (NCB - 1) + 32 (NCB = 3:
+// 64 x 292 x 4 = 73 KiB, two workgroups per CU; N = 258 is such a width).
+// TRIPS: 16-B store trips per thread that cover 64 rows x COLS columns.
+template <int NCB, bool SLIM = false>
 struct MlpSmem {
-  static constexpr int OUT_LD = NCB * 128 + 4;
-  static constexpr int BYTES = kMlpBM * OUT_LD * 4 > 2 * 2 * kMlpBM * 128 ? kMlpBM * OUT_LD * 4 : 2 * 2 * kMlpBM * 128;
+  static constexpr int COLS = SLIM ? (NCB - 1) * 128 + 32 : NCB * 128;
+  static constexpr int TRIPS = kMlpBM * (COLS / 4) / kMlpThreads;
+  static constexpr int BYTES =
+      kMlpBM * (COLS + 4) * 4 > 2 * 2 * kMlpBM * 128 ? kMlpBM * (COLS + 4) * 4 : 2 * 2 * kMlpBM * 128;
 };
+// the widths of an NCB-block problem that fit the SLIM class
+constexpr bool mlp_slim_fits(int ncb, int n) { return (n + 3) / 4 * 4 <= (ncb - 1) * 128 + 32; }
+// The problems that run in it: NCB = 3, the one width class whose tile and not
+// its registers sets the workgroups per CU (97 KiB: one; 73 KiB: two), without
+// an A mask: the masked form's mask stages take it past 256 registers (282),
+// so it would still run one workgroup per CU and stays in the full class.
+constexpr bool mlp_slim_class(int ncb, bool has_mask, int n) { return ncb == 3 && !has_mask && mlp_slim_fits(3, n); }
 
 // One workgroup's rows [bid * kMlpBM, +kMlpBM) of one problem; smem_raw holds
-// MlpSmem<NCB>::BYTES.  GROUPED: the workgroup owns the 4 NCB image blocks
+// MlpSmem<NCB, SLIM>::BYTES (SLIM: the caller checked mlp_slim_fits).
+// A column block that lies wholly at or past N (a ragged last unit: blocks
+// 9..11 of N = 258 belong to waves 1..3) is skipped by its wave: only a
+// wave's LAST block can be such a block (a narrower problem runs a smaller
+// NCB, a group owns whole units below NBp), so the wave picks, once and
+// wave-uniformly, the main loop compiled for NCB or for NCB - 1 live blocks.
+// Either loop is branch-free as before, and a live block's k-steps, their
+// order and its three MFMAs per step are the same in both: the skip changes
+// no output bit.  A skipped block loads no B fragment, issues no MFMA and
+// writes no tile column (the stores never read one: its columns are >= n4).
+// SLIM (ungrouped): the last unit is one real block, 4 (NCB - 1), and a
+// whole-block deal would give all of it to wave 0 (6 MFMA tiles of 32 x 32
+// against 4 on the other waves, and 96 accumulator registers for every wave
+// of the kernel).  Its two row halves go to waves 0 and 1 instead: wave w < 2
+// owns the tile (rows 32 w .., block 4 (NCB - 1)) as the one tile of its last
+// block, waves 2 and 3 skip the block.  5 + 5 + 4 + 4 tiles, 80 accumulator
+// registers; B fragments are prefetched 2 k-steps ahead instead of 3 (a
+// quarter fewer in flight), which brings the class under 256 registers: two
+// waves per SIMD to go with its two tiles per CU.  Which wave runs a tile's
+// MFMA chain does not change the chain.
+// GROUPED: the workgroup owns the 4 NCB image blocks
 // from cb0 (a multiple of 4, cb0 + 4 NCB <= NBp), i.e. columns [32 cb0,
 // min(N, 32 cb0 + 128 NCB)) of B, bias, cmask, C and parts; everything else
 // (the A stages, the k-steps and their order, the three MFMAs per step) is the
 // ungrouped code, so an output element does not depend on the grouping.
-template <int NCB, bool HAS_MASK, bool GROUPED = false>
+template <int NCB, bool HAS_MASK, bool GROUPED = false, bool SLIM = false>
 __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t bid, char* smem_raw,
                                                const int cb0 = 0) {
-  constexpr int OUT_LD = MlpSmem<NCB>::OUT_LD;
   char (*smem)[2 * kMlpBM * 128] = reinterpret_cast<char (*)[2 * kMlpBM * 128]>(smem_raw);
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -208,18 +248,12 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   // ---- B fragments: k-step ks, block i (column block wave + 4 i), plane p ----
   const bf16x8* img = reinterpret_cast<const bf16x8*>(a.img) + lane + (GROUPED ? cb0 * 2 * 64 : 0);
   const int64_t kstride = static_cast<int64_t>(a.NBp) * 2 * 64;  // bf16x8 per k-step
-  bf16x8 bq[4][NCB][2];  // k-step ks in slot ks % 4 (static under the 2-stage unroll)
-  auto load_b = [&](int ks, auto slot_c) {
-    constexpr int SL = decltype(slot_c)::value;
-    const int kc = ks < a.KSp ? ks : a.KSp - 1;  // past the end: a harmless re-read
-#pragma unroll
-    for (int i = 0; i < NCB; ++i) {
-      const bf16x8* p = img + kc * kstride + ((wave + 4 * i) * 2) * 64;
-      bq[SL][i][0] = p[0];
-      bq[SL][i][1] = p[64];
-    }
-  };
 
+  static_assert(!(SLIM && GROUPED), "the slim class is an ungrouped one");
+  // block i of this wave; SLIM: its last is the unit's one real block, of
+  // which the wave owns row half `wave` (acc[0][NCB - 1]; acc[1][NCB - 1] unused)
+  auto blk = [&](int i) { return SLIM && i == NCB - 1 ? 4 * (NCB - 1) : wave + 4 * i; };
+  constexpr int PF = SLIM ? 2 : 3;  // k-steps a B fragment is loaded ahead of its use
   f32x16 acc[kMlpRB][NCB];
 #pragma unroll
   for (int rb = 0; rb < kMlpRB; ++rb)
@@ -232,56 +266,90 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   float bias[NCB];
 #pragma unroll
   for (int i = 0; i < NCB; ++i) {
-    const int col = c0 + (wave + 4 * i) * 32 + l32;
+    const int col = c0 + blk(i) * 32 + l32;
     bias[i] = (a.bias && col < a.N) ? a.bias[col] : 0.0f;
   }
-  load_b(0, std::integral_constant<int, 0>());
-  load_b(1, std::integral_constant<int, 1>());
-  load_b(2, std::integral_constant<int, 2>());
-  fetch_a(0, std::integral_constant<int, 0>());
-  fetch_a(kMlpBK, std::integral_constant<int, 1>());
-  stash_a(0, std::integral_constant<int, 0>(), 0);
-  __syncthreads();
-  // stage st (parity PAR): A of stage st + 1 sits in ra[1 - PAR], stage st + 2
-  // is fetched into ra[PAR]; k-steps 4 st .. 4 st + 3 use B slots 0..3 and
-  // prefetch k-steps 4 st + 3 .. 4 st + 6.
-  auto stage = [&](int st, auto par_c) {
-    constexpr int PAR = decltype(par_c)::value;
-    fetch_a((st + 2) * kMlpBK, std::integral_constant<int, PAR>());
-    const char* base = smem[PAR];
+  // The main loop for a wave with LIVE live blocks (its first LIVE of NCB).
+  // Every wave of the workgroup passes the same barriers in either form: the
+  // A stages and their hand-offs do not depend on LIVE.
+  auto main_loop = [&](auto live_c) {
+    constexpr int LIVE = decltype(live_c)::value;
+    bf16x8 bq[4][LIVE > 0 ? LIVE : 1][2];  // k-step ks in slot ks % 4 (static under the 2-stage unroll)
+    auto load_b = [&](int ks, auto slot_c) {
+      constexpr int SL = decltype(slot_c)::value;
+      const int kc = ks < a.KSp ? ks : a.KSp - 1;  // past the end: a harmless re-read
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int ks = 4 * st + kk;
-      if (kk == 0) load_b(ks + 3, std::integral_constant<int, 3>());
-      if (kk == 1) load_b(ks + 3, std::integral_constant<int, 0>());
-      if (kk == 2) load_b(ks + 3, std::integral_constant<int, 1>());
-      if (kk == 3) load_b(ks + 3, std::integral_constant<int, 2>());
-      if (ks >= ks_end) continue;  // the zero padding of the last stage (uniform)
-      bf16x8 ah[kMlpRB], al[kMlpRB];
-#pragma unroll
-      for (int rb = 0; rb < kMlpRB; ++rb) {
-        const int row = 32 * rb + l32, chunk = 2 * kk + h;
-        ah[rb] = *reinterpret_cast<const bf16x8*>(base + a_lds_off(0, row, chunk));
-        al[rb] = *reinterpret_cast<const bf16x8*>(base + a_lds_off(1, row, chunk));
+      for (int i = 0; i < LIVE; ++i) {
+        const bf16x8* p = img + kc * kstride + (blk(i) * 2) * 64;
+        bq[SL][i][0] = p[0];
+        bq[SL][i][1] = p[64];
       }
+    };
+    load_b(0, std::integral_constant<int, 0>());
+    load_b(1, std::integral_constant<int, 1>());
+    if constexpr (PF == 3) load_b(2, std::integral_constant<int, 2>());
+    fetch_a(0, std::integral_constant<int, 0>());
+    fetch_a(kMlpBK, std::integral_constant<int, 1>());
+    stash_a(0, std::integral_constant<int, 0>(), 0);
+    __syncthreads();
+    // stage st (parity PAR): A of stage st + 1 sits in ra[1 - PAR], stage st + 2
+    // is fetched into ra[PAR]; k-steps 4 st .. 4 st + 3 use B slots 0..3 and
+    // prefetch k-steps 4 st + PF .. 4 st + PF + 3.
+    auto stage = [&](int st, auto par_c) {
+      constexpr int PAR = decltype(par_c)::value;
+      fetch_a((st + 2) * kMlpBK, std::integral_constant<int, PAR>());
+      const char* base = smem[PAR];
 #pragma unroll
-      for (int i = 0; i < NCB; ++i)
+      for (int kk = 0; kk < 4; ++kk) {
+        const int ks = 4 * st + kk;
+        if (kk == 0) load_b(ks + PF, std::integral_constant<int, PF & 3>());
+        if (kk == 1) load_b(ks + PF, std::integral_constant<int, (PF + 1) & 3>());
+        if (kk == 2) load_b(ks + PF, std::integral_constant<int, (PF + 2) & 3>());
+        if (kk == 3) load_b(ks + PF, std::integral_constant<int, (PF + 3) & 3>());
+        if (ks >= ks_end) continue;  // the zero padding of the last stage (uniform)
+        bf16x8 ah[kMlpRB], al[kMlpRB];
 #pragma unroll
         for (int rb = 0; rb < kMlpRB; ++rb) {
-          acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb], bq[kk][i][0], acc[rb][i], 0, 0, 0);
-          acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb], bq[kk][i][1], acc[rb][i], 0, 0, 0);
-          acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb], bq[kk][i][0], acc[rb][i], 0, 0, 0);
+          const int row = 32 * rb + l32, chunk = 2 * kk + h;
+          ah[rb] = *reinterpret_cast<const bf16x8*>(base + a_lds_off(0, row, chunk));
+          al[rb] = *reinterpret_cast<const bf16x8*>(base + a_lds_off(1, row, chunk));
         }
-    }
-    if (st + 1 < nstage) {
-      stash_a((st + 1) * kMlpBK, std::integral_constant<int, 1 - PAR>(), 1 - PAR);
-      lds_barrier();  // LDS hand-off only: the A / B prefetches stay in flight
+#pragma unroll
+        for (int i = 0; i < LIVE; ++i) {
+          if constexpr (SLIM && LIVE == NCB) {
+            if (i == NCB - 1) {  // the one tile of the last block: row half `wave` (read again: no register select)
+              const int row = 32 * wave + l32, chunk = 2 * kk + h;
+              const bf16x8 ahw = *reinterpret_cast<const bf16x8*>(base + a_lds_off(0, row, chunk));
+              const bf16x8 alw = *reinterpret_cast<const bf16x8*>(base + a_lds_off(1, row, chunk));
+              acc[0][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alw, bq[kk][i][0], acc[0][i], 0, 0, 0);
+              acc[0][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahw, bq[kk][i][1], acc[0][i], 0, 0, 0);
+              acc[0][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahw, bq[kk][i][0], acc[0][i], 0, 0, 0);
+              continue;
+            }
+          }
+#pragma unroll
+          for (int rb = 0; rb < kMlpRB; ++rb) {
+            acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb], bq[kk][i][0], acc[rb][i], 0, 0, 0);
+            acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb], bq[kk][i][1], acc[rb][i], 0, 0, 0);
+            acc[rb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb], bq[kk][i][0], acc[rb][i], 0, 0, 0);
+          }
+        }
+      }
+      if (st + 1 < nstage) {
+        stash_a((st + 1) * kMlpBK, std::integral_constant<int, 1 - PAR>(), 1 - PAR);
+        lds_barrier();  // LDS hand-off only: the A / B prefetches stay in flight
+      }
+    };
+    for (int st = 0; st < nstage; st += 2) {
+      stage(st, std::integral_constant<int, 0>());
+      if (st + 1 < nstage) stage(st + 1, std::integral_constant<int, 1>());
     }
   };
-  for (int st = 0; st < nstage; st += 2) {
-    stage(st, std::integral_constant<int, 0>());
-    if (st + 1 < nstage) stage(st + 1, std::integral_constant<int, 1>());
-  }
+  // the wave's last block starts at or past N: not a column of it is real
+  // (wave-uniform); SLIM: the last block has a tile for waves 0 and 1 only
+  const bool last_dead = SLIM ? wave >= kMlpRB : c0 + (wave + 4 * (NCB - 1)) * 32 >= a.N;
+  if (last_dead) main_loop(std::integral_constant<int, NCB - 1>());
+  else main_loop(std::integral_constant<int, NCB>());
 
   // ---- epilogue: lane (l32, h), register r -> row (r & 3) + 8 (r >> 2) + 4 h, column l32
   // acc (+ bias, relu) -> LDS tile [64][OUT_LD] (column = 32 cb + l32 of this
@@ -297,17 +365,18 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   // (zeros: the image is zero there) when the row pitch has room for them
   // (pitches below kMlpMaxPitch: 64 rows' byte offsets stay below 2^31)
   const int n4 = (N + 3) / 4 * 4;
+  const int OUT_LD = n4 + 4;  // tile pitch: the workgroup's own columns (n4 <= MlpSmem<NCB, SLIM>::COLS)
   const bool v4 = (a.ldc % 4 == 0) && (a.ldc >= c0 + n4) && (a.ldc < kMlpMaxPitch) &&
                   (reinterpret_cast<uintptr_t>(a.C) % 16 == 0) &&
                   (!cm || ((N % 4 == 0) && (a.ldcm % 4 == 0) && (a.ldcm < kMlpMaxPitch) &&
                            (reinterpret_cast<uintptr_t>(a.cmask) % 16 == 0)));
   // Vector trips: a thread's trip t is 16-B element tid + 256 t of the
-  // [rows][n4 / 4] tile, row-major.  The tile has at most 64 x 32 NCB
-  // elements, so kEpiTrips = 8 NCB trips cover it and the loops unroll fully;
+  // [rows][n4 / 4] tile, row-major.  The tile has at most 64 x COLS / 4
+  // elements, so kEpiTrips = COLS / 16 trips cover it and the loops unroll fully;
   // (row, col) start from one division and step by constants of the launch.
   // A trip past the last row loads and stores at kMlpPastEnd: the mask reads
   // zeros without traffic, the store is dropped.
-  constexpr int kEpiTrips = 8 * NCB;
+  constexpr int kEpiTrips = MlpSmem<NCB, SLIM>::TRIPS;
   const int per_row = n4 / 4;
   const int drow = kMlpThreads / per_row, dcol = kMlpThreads - drow * per_row;
   const int row0 = tid / per_row, col0 = tid - row0 * per_row;
@@ -337,16 +406,31 @@ __device__ __forceinline__ void mlp_rows_block(const MlpArgs& a, const int64_t b
   float* tile = reinterpret_cast<float*>(smem_raw);
 #pragma unroll
   for (int i = 0; i < NCB; ++i) {
-    const int col = (wave + 4 * i) * 32 + l32;
+    const int col = blk(i) * 32 + l32;
     const float b = bias[i];
+    // a row holds n4 columns: a lane past them would write into the next row;
+    // a skipped block writes nothing
+    if (col < n4 && !(i == NCB - 1 && last_dead)) {
+      if constexpr (SLIM) {
+        if (i == NCB - 1) {  // one tile: row half `wave`
 #pragma unroll
-    for (int rb = 0; rb < kMlpRB; ++rb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float v = acc[rb][i][r] + b;
-        if (a.relu) v = v > 0.0f ? v : 0.0f;
-        tile[(32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h) * OUT_LD + col] = v;
+          for (int r = 0; r < 16; ++r) {
+            float v = acc[0][i][r] + b;
+            if (a.relu) v = v > 0.0f ? v : 0.0f;
+            tile[(32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h) * OUT_LD + col] = v;
+          }
+          continue;
+        }
       }
+#pragma unroll
+      for (int rb = 0; rb < kMlpRB; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float v = acc[rb][i][r] + b;
+          if (a.relu) v = v > 0.0f ? v : 0.0f;
+          tile[(32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h) * OUT_LD + col] = v;
+        }
+    }
   }
   __syncthreads();
   if (v4) {
@@ -433,10 +517,12 @@ __device__ __forceinline__ void mlp_rows_grouped(const MlpArgs& a, const int id,
   else mlp_rows_block<3, HAS_MASK, true>(a, rb, smem_raw, cb0);
 }
 
-template <int NCB, bool HAS_MASK>
+// SLIM is instantiated where mlp_slim_class says; the grouped and pair kernels
+// keep the full class of their widest problem.
+template <int NCB, bool HAS_MASK, bool SLIM = false>
 __global__ void __launch_bounds__(kMlpThreads) mlp_rows_kernel(const MlpArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem_raw[MlpSmem<NCB>::BYTES];
-  mlp_rows_block<NCB, HAS_MASK>(a, blockIdx.x, smem_raw);
+  __shared__ __attribute__((aligned(16))) char smem_raw[MlpSmem<NCB, SLIM>::BYTES];
+  mlp_rows_block<NCB, HAS_MASK, false, SLIM>(a, blockIdx.x, smem_raw);
 }
 
 template <int XMAX, bool HAS_MASK>
@@ -898,6 +984,128 @@ __global__ void __launch_bounds__(1024) mlp_sum_parts_pair_kernel(const float* _
   else mlp_sum_parts_block(p1, S1, len1, o1, b - split, red);
 }
 
+// 256-thread form of mlp_sum_parts_block for a launch whose other block roles
+// are 256 threads: the same 16 split groups, each summed from 0 in split
+// order, then the 16 group sums added in group order, then the same Adagrad
+// arithmetic on operands loaded with the partials — bit-identical.  Thread
+// (q4, lane) adds groups 4 q4 .. 4 q4 + 3, their loads in flight together.
+__device__ __forceinline__ void mlp_sum_parts_block256(const float* __restrict__ parts, int S, int64_t len,
+                                                       float* __restrict__ out, const int64_t bid, f32x4 (*red)[64],
+                                                       const PartsAdagrad& ad) {
+  const int lane = threadIdx.x & 63, q4 = threadIdx.x >> 6;
+  const int64_t e4 = (bid * 64 + lane) * 4;
+  const int per = (S + 15) / 16;
+  const bool apply = ad.param != nullptr && q4 == 0 && e4 < len;
+  f32x4 pa = {0.0f, 0.0f, 0.0f, 0.0f}, ac = pa;
+  if (apply) {
+    pa = *reinterpret_cast<const f32x4*>(ad.param + e4);
+    ac = *reinterpret_cast<const f32x4*>(ad.accum + e4);
+  }
+  f32x4 acc[4];
+#pragma unroll
+  for (int gg = 0; gg < 4; ++gg) acc[gg] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  if (e4 < len) {
+    for (int o = 0; o < per; o += 8) {
+      f32x4 v[4][8];
+#pragma unroll
+      for (int gg = 0; gg < 4; ++gg) {
+        const int s0 = (4 * q4 + gg) * per, s1 = min(S, s0 + per);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (s0 + o + u < s1) v[gg][u] = *reinterpret_cast<const f32x4*>(parts + (s0 + o + u) * len + e4);
+      }
+#pragma unroll
+      for (int gg = 0; gg < 4; ++gg) {
+        const int s0 = (4 * q4 + gg) * per, s1 = min(S, s0 + per);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (s0 + o + u < s1) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[gg][q] += v[gg][u][q];
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int gg = 0; gg < 4; ++gg) red[4 * q4 + gg][lane] = acc[gg];
+  __syncthreads();
+  if (q4 == 0 && e4 < len) {
+    f32x4 t = red[0][lane];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) {
+      const f32x4 r = red[g][lane];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) t[q] += r[q];
+    }
+    *reinterpret_cast<f32x4*>(out + e4) = t;
+    if (apply) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float gi = t[q];
+        const float a = ac[q] + gi * gi;
+        ac[q] = a;
+        pa[q] = pa[q] - (gi * ad.lr) / (sqrtf(a) + ad.eps);
+      }
+      *reinterpret_cast<f32x4*>(ad.accum + e4) = ac;
+      *reinterpret_cast<f32x4*>(ad.param + e4) = pa;
+    }
+  }
+}
+
+// A layer's pending partial sums (+ its Adagrad step): the sum launch of
+// tt_mlp_wgrad(_adagrad) as a block role of another launch.
+struct SumJob {
+  const float* parts;
+  int S;
+  int64_t len;
+  float* out;
+  PartsAdagrad ad;
+};
+
+// One Dense layer's backward as ONE launch of independent block roles:
+// [0, nw) the layer's weight-gradient split partials (mlp_wgrad_block, the
+// default tile of its kind: 128 x 64 masked, 64 x 128 unmasked),
+// [nw, nw + nr) the input-gradient GEMM of the layer below (mlp_rows_block;
+// WC = 0: none, 1..3: NCB = WC, 4: NCB = 3 in the SLIM class), then the
+// previous (upper) layer's partial sums + Adagrad (the grid ends before them
+// when there are none).
+// INVARIANT: no data flows between the roles inside a launch.  The
+// input-gradient role reads the packed weight IMAGE of its layer (written by
+// the step's forward), never the parameters the sum role updates; the sum role
+// reads the partials of the PREVIOUS launch, never those the weight-gradient
+// role writes (tt_mlp_backward_layer refuses overlapping buffers).
+// LDS: the largest role's (the weight-gradient stages are 64 KiB, the rows
+// tile 66.5 KiB at WC = 2 and 73 KiB at WC = 4), each role carving the one
+// buffer its own way; at most 256 registers: two workgroups per CU except at
+// WC = 3 (97 KiB, over 256 registers: one).
+template <bool WMASK, int WC, bool RMASK>
+__global__ void __launch_bounds__(kWgThreads, WC == 3 ? 1 : 2) mlp_bwd_layer_kernel(const WgradArgs w, const int nw,
+                                                                       const MlpArgs r, const int nr,
+                                                                       const SumJob sj) {
+  static_assert(kWgThreads == kMlpThreads, "one block size for every role");
+  constexpr int WI = WMASK ? 2 : 1, WJ = WMASK ? 1 : 2;
+  constexpr int NCB = WC > 3 ? 3 : WC;
+  constexpr bool SLIM = WC == 4;
+  constexpr int WB = 2 * kWgStageB<WI, WJ>, RB = WC > 0 ? MlpSmem<(NCB > 0 ? NCB : 1), SLIM>::BYTES : 0,
+                SB = 16 * 64 * static_cast<int>(sizeof(f32x4));
+  constexpr int BYTES = WB > RB ? (WB > SB ? WB : SB) : (RB > SB ? RB : SB);
+  __shared__ __attribute__((aligned(16))) char smem[BYTES];
+  int b = blockIdx.x;
+  if (b < nw) {
+    mlp_wgrad_block<WMASK, WI, WJ>(w, b, smem);
+    return;
+  }
+  b -= nw;
+  if constexpr (WC > 0) {
+    if (b < nr) {
+      mlp_rows_block<NCB, RMASK, false, SLIM>(r, b, smem);
+      return;
+    }
+    b -= nr;
+  }
+  mlp_sum_parts_block256(sj.parts, sj.S, sj.len, sj.out, b, reinterpret_cast<f32x4(*)[64]>(smem), sj.ad);
+}
+
 __global__ void __launch_bounds__(256) mlp_pack_kernel(const float* __restrict__ w, int64_t ldw, int K, int N,
                                                        int trans, int KS, int NB, __bf16* __restrict__ img) {
   const int64_t t = blockIdx.x * 256ll + threadIdx.x;
@@ -1024,6 +1232,7 @@ static void launch_rows(const MlpArgs& a, int ncb, hipStream_t st) {
   }
   if (ncb == 1) hipLaunchKernelGGL((mlp_rows_kernel<1, HM>), grid, dim3(kMlpThreads), 0, st, a);
   else if (ncb == 2) hipLaunchKernelGGL((mlp_rows_kernel<2, HM>), grid, dim3(kMlpThreads), 0, st, a);
+  else if (mlp_slim_class(ncb, HM, a.N)) hipLaunchKernelGGL((mlp_rows_kernel<3, false, true>), grid, dim3(kMlpThreads), 0, st, a);
   else hipLaunchKernelGGL((mlp_rows_kernel<3, HM>), grid, dim3(kMlpThreads), 0, st, a);
 }
 
@@ -1134,9 +1343,10 @@ extern "C" size_t tt_mlp_wgrad_workspace_size(int64_t M, int32_t Ka, int32_t N) 
 struct WgradTile {
   int wi, wj;
 };
+static WgradTile wgrad_default_tile(bool masked) { return masked ? WgradTile{2, 1} : WgradTile{1, 2}; }
 static WgradTile wgrad_tile(bool masked) {
   const char* e = std::getenv("TT_WGRAD_TILE");
-  if (!e || !*e) return masked ? WgradTile{2, 1} : WgradTile{1, 2};
+  if (!e || !*e) return wgrad_default_tile(masked);
   if (!std::strcmp(e, "128")) return {2, 2};
   if (!std::strcmp(e, "64")) return {1, 1};
   if (!std::strcmp(e, "128x64")) return {2, 1};
@@ -1293,6 +1503,108 @@ extern "C" int tt_mlp_wgrad_pair(const tt_mlp_wgrad_problem* p, void* workspace,
   const int sb0 = static_cast<int>(ceil_div(len0, 256));
   hipLaunchKernelGGL(mlp_sum_parts_pair_kernel, dim3(static_cast<unsigned>(sb0 + ceil_div(len1, 256))), dim3(1024), 0,
                      st, a[0].parts, a[0].S, len0, p[0].dwb, a[1].parts, a[1].S, len1, p[1].dwb, sb0);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+// ---- one Dense layer's backward in one launch ------------------------------
+namespace {
+
+// One weight-gradient job into its kernel arguments (the default tile of its
+// kind: every tile is bit-identical, TT_WGRAD_TILE picks among the separate
+// launches only) and its sum role.
+int wgrad_job_setup(const char* fn, const tt_mlp_wgrad_job* j, WgradArgs& a, SumJob& s) {
+  const tt_mlp_wgrad_problem& q = j->p;
+  if (int rc = wgrad_setup(fn, q.A, q.lda, q.G, q.ldg, q.gmask, q.ldgm, q.scale, q.M, q.Ka, q.N, q.dwb,
+                           wgrad_default_tile(q.gmask != nullptr), a))
+    return rc;
+  const size_t need = tt_mlp_wgrad_workspace_size(q.M, q.Ka, q.N);
+  TT_REQUIRE(j->parts && j->parts_bytes >= need, "%s: partials buffer %zu < %zu bytes", fn, j->parts_bytes, need);
+  TT_REQUIRE(reinterpret_cast<uintptr_t>(q.dwb) % 16 == 0 && reinterpret_cast<uintptr_t>(j->parts) % 16 == 0,
+             "%s: dwb / parts must be 16-B aligned", fn);
+  TT_REQUIRE(!j->param || (j->accum && reinterpret_cast<uintptr_t>(j->param) % 16 == 0 &&
+                           reinterpret_cast<uintptr_t>(j->accum) % 16 == 0),
+             "%s: Adagrad param / accum must both be set and 16-B aligned", fn);
+  a.parts = static_cast<float*>(j->parts);
+  s = SumJob{a.parts, a.S, static_cast<int64_t>(q.Ka + 1) * q.N, q.dwb,
+             PartsAdagrad{j->param, j->param ? j->accum : nullptr, j->lr, j->eps}};
+  return TT_OK;
+}
+
+template <bool WM, int WC>
+void launch_bwd2(bool rm, const WgradArgs& w, int nw, const MlpArgs& r, int nr, const SumJob& s, dim3 grid,
+                 hipStream_t st) {
+  if (rm) hipLaunchKernelGGL((mlp_bwd_layer_kernel<WM, WC, true>), grid, dim3(kWgThreads), 0, st, w, nw, r, nr, s);
+  else hipLaunchKernelGGL((mlp_bwd_layer_kernel<WM, WC, false>), grid, dim3(kWgThreads), 0, st, w, nw, r, nr, s);
+}
+
+// wc: the rows role's width class (mlp_bwd_layer_kernel's WC)
+template <bool WM>
+void launch_bwd1(int wc, bool rm, const WgradArgs& w, int nw, const MlpArgs& r, int nr, const SumJob& s, dim3 grid,
+                 hipStream_t st) {
+  switch (wc) {
+    case 0: launch_bwd2<WM, 0>(false, w, nw, r, nr, s, grid, st); break;
+    case 1: launch_bwd2<WM, 1>(rm, w, nw, r, nr, s, grid, st); break;
+    case 2: launch_bwd2<WM, 2>(rm, w, nw, r, nr, s, grid, st); break;
+    case 3: launch_bwd2<WM, 3>(rm, w, nw, r, nr, s, grid, st); break;
+    default:  // the slim class has no A mask (mlp_slim_class)
+      hipLaunchKernelGGL((mlp_bwd_layer_kernel<WM, 4, false>), grid, dim3(kWgThreads), 0, st, w, nw, r, nr, s);
+      break;
+  }
+}
+
+}  // namespace
+
+extern "C" int tt_mlp_backward_layer(const tt_mlp_wgrad_job* w, const tt_mlp_rows_problem* r,
+                                     const tt_mlp_wgrad_job* prev, tt_stream_t stream) {
+  clear_error();
+  const char* fn = "tt_mlp_backward_layer";
+  TT_REQUIRE(w, "%s: NULL weight-gradient job", fn);
+  WgradArgs wa;
+  SumJob cur;
+  if (int rc = wgrad_job_setup(fn, w, wa, cur)) return rc;
+  MlpArgs ra{};
+  int ncb = 0;
+  const bool has_r = r != nullptr && r->M > 0;
+  if (has_r) {
+    if (int rc = rows_setup(fn, r->A, r->lda, r->amask, r->ldam, r->scale, r->M, r->K, r->img, r->N, r->bias, r->relu,
+                            r->cmask, r->ldcm, r->C, r->ldc, ra, ncb))
+      return rc;
+    if (ra.G > 1) return fail(TT_ERR_UNSUPPORTED, "%s: input-gradient width %d > %d runs as tt_mlp_rows", fn, ra.N,
+                              kMlpMaxCB * 128);
+  }
+  SumJob ps{};
+  int64_t ns = 0;
+  if (prev) {
+    WgradArgs pa;
+    if (int rc = wgrad_job_setup(fn, prev, pa, ps)) return rc;
+    // the previous layer's partials are read while this layer's are written
+    const char *p0 = static_cast<const char*>(prev->parts), *w0 = static_cast<const char*>(w->parts);
+    const size_t pn = tt_mlp_wgrad_workspace_size(prev->p.M, prev->p.Ka, prev->p.N),
+                 wn = tt_mlp_wgrad_workspace_size(w->p.M, w->p.Ka, w->p.N);
+    TT_REQUIRE(p0 + pn <= w0 || w0 + wn <= p0, "%s: the previous layer's partials overlap this layer's", fn);
+    ns = ceil_div(ps.len, 256);
+  }
+  const int nw = wa.S * wa.TI * wa.TJ;
+  const int nr = has_r ? static_cast<int>(ceil_div(ra.M, kMlpBM)) : 0;
+  const dim3 grid(static_cast<unsigned>(nw + nr + ns));
+  hipStream_t st = to_stream(stream);
+  const bool rm = has_r && ra.amask != nullptr;
+  const int wc = !has_r ? 0 : (mlp_slim_class(ncb, rm, ra.N) ? 4 : ncb);
+  if (wa.gmask) launch_bwd1<true>(wc, rm, wa, nw, ra, nr, ps, grid, st);
+  else launch_bwd1<false>(wc, rm, wa, nw, ra, nr, ps, grid, st);
+  TT_CHECK_LAUNCH();
+  return TT_OK;
+}
+
+extern "C" int tt_mlp_wgrad_finish(const tt_mlp_wgrad_job* w, tt_stream_t stream) {
+  clear_error();
+  TT_REQUIRE(w, "tt_mlp_wgrad_finish: NULL job");
+  WgradArgs wa;
+  SumJob s;
+  if (int rc = wgrad_job_setup("tt_mlp_wgrad_finish", w, wa, s)) return rc;
+  hipLaunchKernelGGL(mlp_sum_parts_kernel, dim3(static_cast<unsigned>(ceil_div(s.len, 256))), dim3(1024), 0,
+                     to_stream(stream), s.parts, s.S, s.len, s.out, s.ad);
   TT_CHECK_LAUNCH();
   return TT_OK;
 }

@@ -14,7 +14,9 @@ step is a single tt_dense_* launch.  Every GEMM is libtt's, on bf16x3 MFMA
     straight into the flat gradient (the top layer's ReluGrad and loss scale
     applied inside its loads), then ONE tt_mlp_rows for the layer below with
     the ReluGrad mask fused (G_{l-1} = (G_l W_l^T) * relu'(h_{l-1})), or the
-    input gradient of the first layer;
+    input gradient of the first layer; by default the two and the upper
+    layer's partial sums share ONE launch per layer (tt_mlp_backward_layer,
+    DenseStack._one_launch says when not), bit-identical to the separate ones;
   * forward_acts_pair / backward_acts_pair: the same per-layer work of the
     query and the candidate tower as ONE launch per layer and kind
     (tt_mlp_rows_pair, tt_mlp_wgrad_pair) on one stream, bit-identical to the
@@ -158,6 +160,9 @@ class DenseStack:
         # FUSED_DENSE_WGRAD); the layers it was applied to in this backward
         self.fused_adagrad = None
         self.fused_applied: set = set()
+        # True while a train step applies each tower's whole update inside the
+        # backward (TwoTowerModel: fused_optimizer_apply): _one_launch
+        self.separate_launches = False
 
     def params(self, flat: Optional[torch.Tensor] = None):
         f = self.flat if flat is None else flat
@@ -287,6 +292,11 @@ class DenseStack:
         its loads), then ONE tt_mlp_rows for the layer below:
         G_{l-1} = (G_l W_l^T) * relu'(h_{l-1}) (the top layer's relu mask and
         scale applied to its A loads), or the input gradient dx = G_1 W_1^T.
+        By default the two, and the upper layer's partial sums + Adagrad,
+        are ONE tt_mlp_backward_layer launch per layer and the last layer's
+        sums a tt_mlp_wgrad_finish (three launches for a two-layer tower
+        instead of six, bit-identical; _one_launch says which layers keep the
+        separate launches).
         gout is not modified.  A layer outside tt_mlp_wgrad's alignment
         contract (output width not a multiple of 4) runs it on zero-padded
         copies (_wgrad_padded).  Images: packed by this step's forward
@@ -304,16 +314,56 @@ class DenseStack:
             return dx, finish()
         gflat = torch.empty_like(flat)
         g = gout
+        prev = None  # the job whose partial sums (+ Adagrad) the next launch adds
         for li in range(len(self.layout) - 1, -1, -1):
-            self._wgrad_layer(li, acts, gflat, gout, g, gscale)
-            if li == 0 and not need_input_grad:
-                g = None
-                break
-            p = self._igrad_problem(li, acts, g, gscale)
-            g = _rows(p)
+            want_rows = li > 0 or need_input_grad
+            if self._one_launch(li, acts, gflat, g):
+                # one launch: this layer's weight-gradient partials, the layer
+                # below's input gradient and the upper layer's sums + Adagrad
+                job = self._wgrad_job(li, acts, gflat, gout, g, gscale)
+                rows = self._igrad_problem(li, acts, g, gscale) if want_rows else None
+                hip_ops.mlp_backward_layer(job, rows, prev)
+                prev = job
+                g = rows["out"] if rows is not None else None
+            else:
+                if prev is not None:
+                    hip_ops.mlp_wgrad_finish(prev)
+                    prev = None
+                self._wgrad_layer(li, acts, gflat, gout, g, gscale)
+                g = _rows(self._igrad_problem(li, acts, g, gscale)) if want_rows else None
+        if prev is not None:
+            hip_ops.mlp_wgrad_finish(prev)
         if on_dx is not None:
             on_dx(g)
         return g, gflat
+
+    def _one_launch(self, li: int, acts, gflat, g) -> bool:
+        """Layer li's backward runs as one tt_mlp_backward_layer launch (the
+        default two-stream path); the separate launches keep:
+          * TT_TOWER_PAIR: backward_acts_pair already shares each launch between the towers;
+          * TT_IGRAD_FIRST: backward_split runs the two kinds in two phases, nothing to share;
+          * fused_optimizer_apply: its step was measured with the separate chain only;
+          * input widths over 384: that input gradient is a grouped launch of (rows x column groups);
+          * a region of the flat buffer that is not 16-B aligned, or operands
+            outside tt_mlp_wgrad's contract: the sum role's vector accesses
+            (the layers _layer_adagrad and _wgrad_padded route away)."""
+        if self.separate_launches:
+            return False
+        w_off, fi, fo, _ = self.layout[li]
+        if fi > 384 or not self._wgrad_fits(li, g, acts):
+            return False
+        ptrs = [gflat.data_ptr()]
+        if self.fused_adagrad is not None:
+            ptrs += [self.flat.data_ptr(), self.fused_adagrad[0].data_ptr()]
+        return all((p + 4 * w_off) % 16 == 0 for p in ptrs)
+
+    def _wgrad_job(self, li, acts, gflat, gout, g, gscale):
+        """Layer li's weight gradient (+ its fused Adagrad step) as a
+        tt_mlp_wgrad_job; the partials alternate between two workspaces by
+        layer parity (a job's partials are summed by the next launch)."""
+        p = self._wgrad_problem(li, acts, gflat, gout, g, gscale)
+        return hip_ops.mlp_wgrad_job(p["a"], p["g"], p["dwb"], gmask=p.get("gmask"), scale=p.get("scale"),
+                                     adagrad=self._layer_adagrad(li), tag=f"mlp_wgrad_l{li % 2}")
 
     def backward_split(self, acts: List[torch.Tensor], flat: torch.Tensor, gout: torch.Tensor,
                        gscale: Optional[torch.Tensor], need_input_grad: bool):

@@ -495,6 +495,7 @@ class TwoTowerModel(AbstractKerasModel):
         for t in self.towers:
             t.dense.fused_applied = set()
             t.dense.fused_adagrad = None
+            t.dense.separate_launches = bool(fused)
             if dense_early and FUSED_DENSE_WGRAD:
                 opt = self.optimizer
                 (acc,) = opt._slot(t.dense.flat, 1, opt.initial_accumulator_value)
