@@ -11,14 +11,17 @@ gradient.  The [B, B] score matrix never exists.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import os
+import types
 
 from typing import Optional
 
 import torch
 
 from pkg.modelling import hip_ops
+from pkg.modelling.models.tower import backward_acts_pair, forward_acts_pair, pair_compatible
 
 __all__ = ["InBatchSoftmaxCrossEntropy", "inbatch_softmax_xent", "towers_inbatch_softmax_xent",
            "global_inbatch_grads", "global_towers_inbatch_softmax_xent", "weighted_inbatch_grads", "TOWER_C_SCOPE"]
@@ -184,28 +187,32 @@ TOWER_PAIR = int(os.environ.get("TT_TOWER_PAIR", "0"))
 
 
 def _paired(x: torch.Tensor, stack_q, stack_c) -> bool:
-    from pkg.modelling.models.tower import pair_compatible
     return bool(TOWER_PAIR) and x.is_cuda and pair_compatible(stack_q, stack_c)
 
 
-def _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c):
-    from pkg.modelling.models.tower import forward_acts_pair
-    return forward_acts_pair((stack_q, stack_c), (qi, ci), (flat_q, flat_c))
+def _hooks(step):
+    """(on_tower, on_dx, (the query tower's TowerStep, the candidate tower's))
+    of a train step's state (TwoTowerModel.TrainStep); of None: nothing."""
+    return (None, None, (None, None)) if step is None else (step.on_tower, step.on_dx, step.towers)
 
 
-def _pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, on_tower=None):
-    """Both towers' backward as paired launches; on_tower(1, ...) runs in the
-    candidate tower's workspace scope (where its update was prepared)."""
-    from pkg.modelling.models.tower import backward_acts_pair
-    stack_q, stack_c = ctx.stacks
-    (gqi, gflat_q), (gci, gflat_c) = backward_acts_pair(
-        (stack_q, stack_c), (qa, ca), (flat_q, flat_c), (dq, dc), s,
-        (ctx.needs_input_grad[0], ctx.needs_input_grad[1]))
-    if on_tower is not None:
-        with hip_ops.Workspace.scope(TOWER_C_SCOPE):
-            on_tower(1, gci, gflat_c)
-        on_tower(0, gqi, gflat_q)
-    return gqi, gci, gflat_q, gflat_c
+def _both_towers(fork: bool, device: torch.device, tower):
+    """(tower(0), tower(1)): the candidate tower's work, tower(1), issued
+    first in its workspace scope and, with `fork`, on its own stream forked
+    from the current one; then the query tower's, tower(0), on the current
+    stream; then the join, from the fork's origin (a captured branch must not
+    join a sub-branch itself)."""
+    with contextlib.ExitStack() as block:
+        block.enter_context(hip_ops.Workspace.scope(TOWER_C_SCOPE))
+        if fork:
+            side = _tower_stream(device)
+            side.wait_stream(torch.cuda.current_stream())
+            block.enter_context(torch.cuda.stream(side))
+        cand = tower(1)
+    query = tower(0)
+    if fork:
+        torch.cuda.current_stream().wait_stream(side)
+    return query, cand
 
 
 def normalized_outputs(stack_q, stack_c, q: torch.Tensor, c: torch.Tensor):
@@ -236,38 +243,6 @@ def unnormalize_grads(stack_q, stack_c, q: torch.Tensor, c: torch.Tensor, invs, 
         hip_ops.l2norm_rows_grad(jobs)
 
 
-class _TowerFork:
-    """Work in this block runs on the candidate tower's stream (forked from the
-    current one) and workspace scope; plain on CPU tensors."""
-
-    def __init__(self, like: torch.Tensor):
-        self.cuda = _two_streams(like)
-        self.dev = like.device
-
-    def __enter__(self):
-        self.scope = hip_ops.Workspace.scope(TOWER_C_SCOPE)
-        self.scope.__enter__()
-        if self.cuda:
-            side = _tower_stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream())
-            self.ctx = torch.cuda.stream(side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.cuda:
-            self.ctx.__exit__(*exc)
-        self.scope.__exit__(*exc)
-        return False
-
-
-def _tower_join(like: torch.Tensor) -> None:
-    """The current stream waits for the candidate tower's stream (joined from
-    the fork's origin: a captured branch must not join a sub-branch itself)."""
-    if _two_streams(like):
-        torch.cuda.current_stream().wait_stream(_tower_stream(like.device))
-
-
 def _two_streams(like: torch.Tensor) -> bool:
     return like.is_cuda and GLOBAL_TOWER_STREAMS > 0 and like.shape[0] >= GLOBAL_TOWER_STREAMS
 
@@ -279,87 +254,72 @@ class _TowersInBatchXent(torch.autograd.Function):
     the query tower's (fork / join with stream waits: captured as parallel
     branches of the step's hipGraph).  The backward hands the loss's incoming
     gradient to the top layers' weight-gradient and input-gradient kernels as
-    a device scalar (no separate scaling pass over dQ, dC)."""
+    a device scalar (no separate scaling pass over dQ, dC).
+    After the four tensors: logq, the stacks, the loss scale, and
+      stage(q, c, ws, unnormalize) -> (loss, dq, dc): the loss stage on the
+        towers' (normalised) outputs — the single-device entries or the
+        global-negatives ones; it calls unnormalize(dq, dc) where it wants
+        the gradients taken back to the un-normalised outputs (in place);
+      fork(x) -> bool: whether the towers run on two streams;
+      split_prep: each tower's bf16 loss operand prepared on its own stream
+        right after its MLP, into the workspace `stage` is then given as ws;
+      step: the train step's state (callbacks and per-tower TowerSteps), or None."""
 
     @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower=None, on_dx=None, ids=None,
-                weights=None, weight_scale=1.0, hard=None):
+    def forward(ctx, qi, ci, flat_q, flat_c, *cfg):
+        logq, stack_q, stack_c, ctx.scale, stage, ctx.fork, split_prep, ctx.step = cfg
+        stacks, xs, flats, tsteps = (stack_q, stack_c), (qi, ci), (flat_q, flat_c), _hooks(ctx.step)[2]
         # (extra negatives: the candidate tower runs on more rows, the towers unpaired)
         ctx.pair = _paired(qi, stack_q, stack_c) and qi.shape[0] == ci.shape[0]
-        ctx.on_dx = on_dx
+        ws = None
         if ctx.pair:
-            qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
-            return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower,
-                                              ids=ids, weights=weights, weight_scale=weight_scale, hard=hard)
-        main = torch.cuda.current_stream()
-        side = _tower_stream(qi.device)
-        # SPLIT_PREP: each tower's bf16 copy for the loss is made on its own
-        # stream right after its MLP (the workspace is fetched before the fork)
-        # (not under x3_scores() or with ids: those entries prepare their operands themselves;
-        # not with normalised outputs: it would prepare the un-normalised ones)
-        split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None and hard is None
-                      and not (stack_q.normalize or stack_c.normalize) and qi.shape[0] == ci.shape[0])
-        ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device) if split_prep else None
-        side.wait_stream(main)
-        with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
-            ca = stack_c.forward_acts(ci, flat_c)
-            if ws is not None:
-                hip_ops.inbatch_prep(ca[-1], 1, logq, ws)
-        qa = stack_q.forward_acts(qi, flat_q)
-        if ws is not None:
-            hip_ops.inbatch_prep(qa[-1], 0, None, ws)
-        main.wait_stream(side)
-        return _TowersInBatchXent._finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws,
-                                          ids, weights, weight_scale, hard)
+            qa, ca = forward_acts_pair(stacks, xs, flats, steps=tsteps)
+        else:
+            if split_prep:  # (the workspace is fetched before the fork)
+                ws = hip_ops.inbatch_fused_workspace(qi.shape[0], stack_q.out_dim, qi.device)
 
-    @staticmethod
-    def _finish(ctx, qa, ca, flat_q, flat_c, logq, stack_q, stack_c, scale, on_tower, ws=None, ids=None,
-                weights=None, weight_scale=1.0, hard=None):
-        if weights is not None:
-            scale = scale * weight_scale  # w_max: the loss is linear in w
-        ctx.stacks = (stack_q, stack_c)
-        ctx.nq = len(qa)
-        ctx.scale = scale
-        ctx.on_tower = on_tower
+            def tower(i):
+                acts = stacks[i].forward_acts(xs[i], flats[i], step=tsteps[i])
+                if ws is not None:
+                    hip_ops.inbatch_prep(acts[-1], i, logq if i else None, ws)
+                return acts
+
+            qa, ca = _both_towers(ctx.fork(qi), qi.device, tower)
         # cosine scoring: the loss entries run unchanged on the normalised
         # outputs (one launch for both), and its gradients are taken back to
-        # the un-normalised ones right after it (one launch, in place)
+        # the un-normalised ones after it (one launch, in place)
         q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])
-        if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
-            wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
-            loss = hip_ops.loss_sum(wloss, scale)
-        else:  # (ws: only the plain bf16 loss has its operands prepared on the towers' streams)
-            _, dq, dc, loss = _fused_grads(q, c, logq, ids, hard, x3_scores(), loss_scale=scale, ws=ws)
-        unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
+        loss, dq, dc = stage(q, c, ws, functools.partial(unnormalize_grads, stack_q, stack_c, qa[-1], ca[-1], invs))
+        ctx.stacks, ctx.nq, ctx.k = stacks, len(qa), len(cfg)
         ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         flat_q, flat_c, dq, dc, *acts = ctx.saved_tensors
-        qa, ca = acts[:ctx.nq], acts[ctx.nq:]
+        stacks, flats, gouts, acts = ctx.stacks, (flat_q, flat_c), (dq, dc), (acts[:ctx.nq], acts[ctx.nq:])
         s = (g * ctx.scale if ctx.scale != 1.0 else g).reshape(1).float().contiguous()
-        stack_q, stack_c = ctx.stacks
+        on_tower, on_dx, tsteps = _hooks(ctx.step)
         if ctx.pair:  # (on_dx unused: on_tower then applies each tower's whole update)
-            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s, ctx.on_tower),
-                    None, None, None, None, None, None, None, None, None, None)
-        on_dx = ctx.on_dx
-        main = torch.cuda.current_stream()
-        side = _tower_stream(dq.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side), hip_ops.Workspace.scope(TOWER_C_SCOPE):
-            # this tower's updates (on_dx: the embedding update once its input
-            # gradient exists; on_tower: the rest), beside the other tower's backward
-            gci, gflat_c = stack_c.backward_acts(ca, flat_c, dc, s, ctx.needs_input_grad[1],
-                                                 on_dx=(lambda dx: on_dx(1, dx)) if on_dx is not None else None)
-            if ctx.on_tower is not None:
-                ctx.on_tower(1, gci, gflat_c)
-        gqi, gflat_q = stack_q.backward_acts(qa, flat_q, dq, s, ctx.needs_input_grad[0],
-                                             on_dx=(lambda dx: on_dx(0, dx)) if on_dx is not None else None)
-        if ctx.on_tower is not None:
-            ctx.on_tower(0, gqi, gflat_q)
-        main.wait_stream(side)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None, None
+            (gqi, gflat_q), (gci, gflat_c) = backward_acts_pair(stacks, acts, flats, gouts, s,
+                                                                ctx.needs_input_grad[:2])
+            if on_tower is not None:  # the candidate tower's in its workspace scope (where its update was prepared)
+                with hip_ops.Workspace.scope(TOWER_C_SCOPE):
+                    on_tower(1, gci, gflat_c)
+                on_tower(0, gqi, gflat_q)
+        else:
+            def tower(i):
+                # this tower's updates (on_dx: the embedding update once its input gradient exists;
+                # on_tower: the rest), the candidate tower's beside the query tower's backward
+                out = stacks[i].backward_acts(acts[i], flats[i], gouts[i], s, ctx.needs_input_grad[i],
+                                              on_dx=functools.partial(on_dx, i) if on_dx is not None else None,
+                                              step=tsteps[i])
+                if on_tower is not None:
+                    on_tower(i, *out)
+                return out
+
+            (gqi, gflat_q), (gci, gflat_c) = _both_towers(ctx.fork(dq), dq.device, tower)
+        return (gqi, gci, gflat_q, gflat_c) + (None,) * ctx.k
 
 
 def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor], comm,
@@ -439,70 +399,37 @@ def global_inbatch_grads(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.
     return (row_loss if weights is None else wloss), dq, dc
 
 
-class _GlobalTowersInBatchXent(torch.autograd.Function):
-    """_TowersInBatchXent with global in-batch negatives (global_inbatch_grads):
-    the returned loss is this rank's rows' share; the step sums it (and the
-    gradients) over the ranks."""
-
-    @staticmethod
-    def forward(ctx, qi, ci, flat_q, flat_c, logq, stack_q, stack_c, scale, comm, ids=None, weights=None,
-                weight_scale=1.0, hard=None):
-        if weights is not None:
-            scale = scale * weight_scale
-        ctx.pair = _paired(qi, stack_q, stack_c)
-        if ctx.pair:
-            qa, ca = _pair_forward(qi, ci, flat_q, flat_c, stack_q, stack_c)
-        else:
-            # the two towers' MLPs on two streams, as in _TowersInBatchXent
-            with _TowerFork(qi):
-                ca = stack_c.forward_acts(ci, flat_c)
-            qa = stack_q.forward_acts(qi, flat_q)
-            _tower_join(qi)
-        q, c, invs = normalized_outputs(stack_q, stack_c, qa[-1], ca[-1])  # cosine scoring (as _TowersInBatchXent)
-        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids, weights=weights, num_hard_negatives=hard)
-        unnormalize_grads(stack_q, stack_c, qa[-1], ca[-1], invs, dq, dc)
-        ctx.stacks = (stack_q, stack_c)
-        ctx.nq = len(qa)
-        ctx.scale = scale
-        ctx.save_for_backward(flat_q, flat_c, dq, dc, *qa, *ca)
-        return hip_ops.loss_sum(row_loss, scale)
-
-    @staticmethod
-    def backward(ctx, g):
-        flat_q, flat_c, dq, dc, *acts = ctx.saved_tensors
-        qa, ca = acts[:ctx.nq], acts[ctx.nq:]
-        s = (g * ctx.scale if ctx.scale != 1.0 else g).reshape(1).float().contiguous()
-        stack_q, stack_c = ctx.stacks
-        if ctx.pair:
-            return (*_pair_backward(ctx, qa, ca, flat_q, flat_c, dq, dc, s), None, None, None, None, None, None,
-                    None, None, None)
-        with _TowerFork(dq):
-            gci, gflat_c = stack_c.backward_acts(ca, flat_c, dc, s, ctx.needs_input_grad[1])
-        gqi, gflat_q = stack_q.backward_acts(qa, flat_q, dq, s, ctx.needs_input_grad[0])
-        _tower_join(dq)
-        return gqi, gci, gflat_q, gflat_c, None, None, None, None, None, None, None, None, None
-
-
 def global_towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c, comm,
                                        logq: Optional[torch.Tensor] = None,
                                        ids: Optional[torch.Tensor] = None,
                                        weights: Optional[torch.Tensor] = None,
                                        weight_scale: float = 1.0,
                                        num_hard_negatives: Optional[int] = None) -> torch.Tensor:
-    """towers_inbatch_softmax_xent with the negatives of every rank (SUM
-    reduction, the reference's runner.py:78-83).  ids: this rank's candidate
-    ids (accidental hits removed over the global batch).  weights: this
-    rank's normalised sample weights, weight_scale the global w_max.
-    num_hard_negatives: hard negatives mined over the global batch."""
-    return _GlobalTowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, 1.0, comm, ids,
-                                          weights, float(weight_scale), _check_hard(num_hard_negatives))
+    """towers_inbatch_softmax_xent with the negatives of every rank
+    (global_inbatch_grads; SUM reduction, the reference's runner.py:78-83):
+    the returned loss is this rank's rows' share; the step sums it (and the
+    gradients) over the ranks.  ids: this rank's candidate ids (accidental
+    hits removed over the global batch).  weights: this rank's normalised
+    sample weights, weight_scale the global w_max.  num_hard_negatives: hard
+    negatives mined over the global batch.  Two streams from
+    GLOBAL_TOWER_STREAMS rows."""
+    hard = _check_hard(num_hard_negatives)
+    scale = 1.0 * float(weight_scale) if weights is not None else 1.0
+
+    def stage(q, c, ws, unnormalize):
+        row_loss, dq, dc = global_inbatch_grads(q, c, logq, comm, ids=ids, weights=weights, num_hard_negatives=hard)
+        unnormalize(dq, dc)
+        return hip_ops.loss_sum(row_loss, scale), dq, dc
+
+    return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, stage,
+                                    _two_streams, False, None)
 
 
 def towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, stack_c,
                                 logq: Optional[torch.Tensor] = None, reduction: str = "sum",
                                 on_tower=None, on_dx=None, ids: Optional[torch.Tensor] = None,
                                 weights: Optional[torch.Tensor] = None, weight_scale: float = 1.0,
-                                num_hard_negatives: Optional[int] = None) -> torch.Tensor:
+                                num_hard_negatives: Optional[int] = None, *, step=None) -> torch.Tensor:
     """Loss of the query tower on qi against the candidate tower on ci (tower
     inputs [B, *]), fused into one autograd node; stack_* are DenseStacks.
     on_tower(i, input_grad, flat_grad), if given, is called in the backward as
@@ -510,12 +437,32 @@ def towers_inbatch_softmax_xent(qi: torch.Tensor, ci: torch.Tensor, stack_q, sta
     workspace scope they were produced in (the fused train step applies the
     optimizer there).  ids [B] (int32): accidental hits removed.  weights [B]
     (fp32, in [0, 1]) and weight_scale: sample weights (see above).
-    num_hard_negatives: hard-negative mining (see above)."""
+    num_hard_negatives: hard-negative mining (see above).  step: a train
+    step's state (TwoTowerModel.TrainStep), which then brings the callbacks."""
     if reduction not in ("sum", "sum_over_batch_size", "mean"):
         raise ValueError(f"unsupported reduction {reduction}")
+    hard = _check_hard(num_hard_negatives)
     scale = 1.0 if reduction == "sum" else 1.0 / qi.shape[0]
-    return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, on_tower,
-                                    on_dx, ids, weights, float(weight_scale), _check_hard(num_hard_negatives))
+    if weights is not None:
+        scale = scale * float(weight_scale)  # w_max: the loss is linear in w
+    if step is None and (on_tower is not None or on_dx is not None):
+        step = types.SimpleNamespace(on_tower=on_tower, on_dx=on_dx, towers=(None, None))
+    # SPLIT_PREP: not under x3_scores() or with ids: those entries prepare their operands themselves;
+    # not with normalised outputs: it would prepare the un-normalised ones
+    split_prep = (SPLIT_PREP and not x3_scores() and ids is None and weights is None and hard is None
+                  and not (stack_q.normalize or stack_c.normalize) and qi.shape[0] == ci.shape[0])
+
+    def stage(q, c, ws, unnormalize):
+        if weights is not None:  # sample weights: rows, fold, cols, tt_sum (either arithmetic, with or without ids)
+            wloss, dq, dc = weighted_inbatch_grads(q, c, logq, weights, ids, num_hard_negatives=hard)
+            loss = hip_ops.loss_sum(wloss, scale)
+        else:  # (ws: only the plain bf16 loss has its operands prepared on the towers' streams)
+            _, dq, dc, loss = _fused_grads(q, c, logq, ids, hard, x3_scores(), loss_scale=scale, ws=ws)
+        unnormalize(dq, dc)
+        return loss, dq, dc
+
+    return _TowersInBatchXent.apply(qi, ci, stack_q.flat, stack_c.flat, logq, stack_q, stack_c, scale, stage,
+                                    lambda x: x.is_cuda, split_prep, step)
 
 
 def inbatch_softmax_xent(q: torch.Tensor, c: torch.Tensor, logq: Optional[torch.Tensor] = None,

@@ -29,6 +29,7 @@ step is a single tt_dense_* launch.  Every GEMM is libtt's, on bf16x3 MFMA
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -39,12 +40,24 @@ from pkg.modelling.device import default_device, make_generator
 from pkg.modelling.layers.input_layer import InputLayer
 from pkg.modelling.models.abstract_keras_model import AbstractKerasModel, TensorSpec
 
-__all__ = ["Tower", "DenseStack", "pair_compatible", "forward_acts_pair", "backward_acts_pair"]
+__all__ = ["Tower", "DenseStack", "TowerStep", "pair_compatible", "forward_acts_pair", "backward_acts_pair"]
 
 # DenseStack.backward_acts: every input gradient before any weight gradient
 # (C3 step, 3 interleaved runs each: unfused 0.535-0.541 vs 0.533-0.536 ms;
 # fused apply 0.570-0.573 vs 0.564-0.565 ms — off)
 IGRAD_FIRST = os.environ.get("TT_IGRAD_FIRST", "0") == "1"
+
+
+@dataclass
+class TowerStep:
+    """One tower's share of one train step's state (TwoTowerModel.train_step
+    makes it; DenseStack's forward and backward take it as step=).  None in
+    its place is a bare stack: the forward packs its own images, the backward
+    may run one launch per layer and applies no Adagrad."""
+    adagrad: Optional[tuple] = None    # (accumulator of flat, lr, eps): applied inside the weight-gradient launches
+    separate_launches: bool = False    # the tower's whole update runs inside the backward: no one-launch layers
+    fused_layers: set = field(default_factory=set)  # the layers whose Adagrad step those launches applied
+    packed: bool = False               # the step's gather launch packed this tower's weight images
 
 
 def check_output_scale(normalize, output_scale) -> Tuple[bool, float]:
@@ -127,8 +140,12 @@ class DenseStack:
     zero), for cosine scoring.  forward_acts / backward_acts are unaffected:
     the stored activations keep the un-normalised top activation (the top
     layer's ReLU mask), and whoever calls them normalises (this class's
-    __call__; the fused loss nodes in losses.py, which normalise both towers'
-    outputs in one launch).  output_scale != 1 needs normalize."""
+    __call__; the fused loss node in losses.py, which normalises both towers'
+    outputs in one launch).  output_scale != 1 needs normalize.
+
+    The stack holds parameters and image buffers only.  What one train step
+    adds (Adagrad inside the weight-gradient launches, separate launches,
+    images packed by the step's gather) arrives as step=, a TowerStep."""
 
     MAX_WIDTH = 4096  # tt_mlp_rows / tt_mlp_wgrad: N, Ka <= 4096
 
@@ -155,14 +172,14 @@ class DenseStack:
             flat[w_off:w_off + fi * fo] = w.reshape(-1)
         self.flat = flat.to(device).requires_grad_(True)
         self.out_dim = fan_in
-        # (accumulator of flat, lr, eps) while a train step applies this
-        # stack's Adagrad inside its weight-gradient launches (TwoTowerModel:
-        # FUSED_DENSE_WGRAD); the layers it was applied to in this backward
-        self.fused_adagrad = None
-        self.fused_applied: set = set()
-        # True while a train step applies each tower's whole update inside the
-        # backward (TwoTowerModel: fused_optimizer_apply): _one_launch
-        self.separate_launches = False
+        # the packed weight images by (kind, layer): buffers made on first use
+        # and kept (fixed addresses, graph-capturable), refilled by every pack
+        self._images: Dict[Tuple[str, int], torch.Tensor] = {}
+
+    @property
+    def images(self) -> Dict[Tuple[str, int], torch.Tensor]:
+        """The packed weight images, as the last pack launch left them."""
+        return self._images
 
     def params(self, flat: Optional[torch.Tensor] = None):
         f = self.flat if flat is None else flat
@@ -171,8 +188,7 @@ class DenseStack:
     def _pack_jobs(self, flat: torch.Tensor) -> Tuple[Dict[Tuple[str, int], torch.Tensor], list]:
         """Image buffers (owned by the stack: fixed addresses, graph-capturable)
         and the tt_mlp_pack_many jobs that fill them from `flat`."""
-        imgs = self.__dict__.setdefault("_images", {})
-        jobs = []
+        imgs, jobs = self._images, []
         for li, (w, _) in enumerate(self.params(flat)):
             for kind, trans in (("f", False), ("t", True)):
                 K, N = (w.shape[1], w.shape[0]) if trans else (w.shape[0], w.shape[1])
@@ -186,24 +202,15 @@ class DenseStack:
     def prepack_jobs(self, flat: torch.Tensor) -> list:
         """The pack jobs of this stack's images for a forward on `flat`, to be
         run by another launch (the train step's gather: hip_ops.gather_multi
-        with pack_jobs); the next forward_acts on the same flat then uses the
-        images as they are (once)."""
-        imgs, jobs = self._pack_jobs(flat)
-        self.__dict__["_prepacked"] = flat.data_ptr()
-        return jobs
-
-    def _images_for(self, flat: torch.Tensor) -> Dict[Tuple[str, int], torch.Tensor]:
-        """This forward's images: prepacked by the gather launch, or packed now."""
-        if self.__dict__.get("_prepacked") == flat.data_ptr():
-            self.__dict__["_prepacked"] = None
-            return self.__dict__["_images"]
-        return self._pack_images(flat)
+        with pack_jobs).  Nothing is recorded here: the step that ran them
+        says so in its TowerStep (packed), and that forward skips its pack."""
+        return self._pack_jobs(flat)[1]
 
     def _pack_images(self, flat: torch.Tensor) -> Dict[Tuple[str, int], torch.Tensor]:
         """Every layer's packed bf16 hi/lo weight images, forward ("f": B = W)
         and transposed ("t": B = W^T, the input-gradient GEMMs), in ONE
-        tt_mlp_pack_many launch.  Packed at the start of each forward, so they
-        always match `flat`."""
+        tt_mlp_pack_many launch.  Packed at the start of each forward (or by
+        that step's gather launch), so they always match `flat`."""
         imgs, jobs = self._pack_jobs(flat)
         for i in range(0, len(jobs), 8):
             hip_ops.mlp_pack_many(jobs[i:i + 8])
@@ -218,9 +225,11 @@ class DenseStack:
         out = torch.empty(h.shape[0], ld, dtype=torch.float32, device=h.device)[:, :n]
         return dict(a=h, img=imgs[("f", li)], k=w.shape[0], n=n, out=out, bias=b, relu=True)
 
-    def forward_acts(self, x: torch.Tensor, flat: torch.Tensor) -> List[torch.Tensor]:
-        """[x, h_1, ..., h_L] with h_l = relu(h_{l-1} W_l + b_l) (tt_mlp_rows)."""
-        imgs = self._images_for(flat)
+    def forward_acts(self, x: torch.Tensor, flat: torch.Tensor, *, step: Optional[TowerStep] = None
+                     ) -> List[torch.Tensor]:
+        """[x, h_1, ..., h_L] with h_l = relu(h_{l-1} W_l + b_l) (tt_mlp_rows).
+        step.packed: the images are this step's already, no pack launch."""
+        imgs = self._images if step is not None and step.packed else self._pack_images(flat)
         acts = [x]
         for li in range(len(self.layout)):
             p = self._fwd_problem(li, acts[-1], flat, imgs)
@@ -280,12 +289,13 @@ class DenseStack:
         amask = acts[-1] if top else None
         if top and fo % 4:  # the joint embedding's rows are not 16-B: aligned copies
             g, amask = _aligned(g), _aligned(amask)
-        return dict(a=g, img=self.__dict__["_images"][("t", li)], k=fo, n=fi, out=out,
+        return dict(a=g, img=self._images[("t", li)], k=fo, n=fi, out=out,
                     amask=amask, scale=gscale if top else None,
                     cmask=acts[li] if li > 0 else None)
 
     def backward_acts(self, acts: List[torch.Tensor], flat: torch.Tensor, gout: torch.Tensor,
-                      gscale: Optional[torch.Tensor], need_input_grad: bool, on_dx=None):
+                      gscale: Optional[torch.Tensor], need_input_grad: bool, on_dx=None, *,
+                      step: Optional[TowerStep] = None):
         """(d x, d flat) from the saved activations.  Per layer l from the top:
         [dW_l; db_l] = [h_{l-1} | 1]^T G_l by ONE tt_mlp_wgrad straight into the
         flat gradient (the top layer's G_L = relu'(h_L) * s * gout formed inside
@@ -304,11 +314,13 @@ class DenseStack:
         before the weight gradients, and on_dx(dx), if given, is called
         between them (the fused step's embedding update); the kernels and
         their results are the same in either order (off by default: same step
-        time unfused, slower fused — DESIGN §9)."""
+        time unfused, slower fused — DESIGN §9).  step: this tower's
+        TowerStep of a train step (its Adagrad inside the weight-gradient
+        launches, separate launches), None for a bare backward."""
         if IGRAD_FIRST:
             # the input-gradient chain first (the embedding update waits for it,
             # the weight gradients do not), on_dx(dx) between the two
-            dx, finish = self.backward_split(acts, flat, gout, gscale, need_input_grad)
+            dx, finish = self.backward_split(acts, flat, gout, gscale, need_input_grad, step=step)
             if on_dx is not None:
                 on_dx(dx)
             return dx, finish()
@@ -317,10 +329,10 @@ class DenseStack:
         prev = None  # the job whose partial sums (+ Adagrad) the next launch adds
         for li in range(len(self.layout) - 1, -1, -1):
             want_rows = li > 0 or need_input_grad
-            if self._one_launch(li, acts, gflat, g):
+            if self._one_launch(li, acts, gflat, g, step=step):
                 # one launch: this layer's weight-gradient partials, the layer
                 # below's input gradient and the upper layer's sums + Adagrad
-                job = self._wgrad_job(li, acts, gflat, gout, g, gscale)
+                job = self._wgrad_job(li, acts, gflat, gout, g, gscale, step=step)
                 rows = self._igrad_problem(li, acts, g, gscale) if want_rows else None
                 hip_ops.mlp_backward_layer(job, rows, prev)
                 prev = job
@@ -329,7 +341,7 @@ class DenseStack:
                 if prev is not None:
                     hip_ops.mlp_wgrad_finish(prev)
                     prev = None
-                self._wgrad_layer(li, acts, gflat, gout, g, gscale)
+                self._wgrad_layer(li, acts, gflat, gout, g, gscale, step=step)
                 g = _rows(self._igrad_problem(li, acts, g, gscale)) if want_rows else None
         if prev is not None:
             hip_ops.mlp_wgrad_finish(prev)
@@ -337,42 +349,43 @@ class DenseStack:
             on_dx(g)
         return g, gflat
 
-    def _one_launch(self, li: int, acts, gflat, g) -> bool:
+    def _one_launch(self, li: int, acts, gflat, g, *, step: Optional[TowerStep] = None) -> bool:
         """Layer li's backward runs as one tt_mlp_backward_layer launch (the
         default two-stream path); the separate launches keep:
           * TT_TOWER_PAIR: backward_acts_pair already shares each launch between the towers;
           * TT_IGRAD_FIRST: backward_split runs the two kinds in two phases, nothing to share;
-          * fused_optimizer_apply: its step was measured with the separate chain only;
+          * fused_optimizer_apply (step.separate_launches): its step was measured with the separate chain only;
           * input widths over 384: that input gradient is a grouped launch of (rows x column groups);
           * a region of the flat buffer that is not 16-B aligned, or operands
             outside tt_mlp_wgrad's contract: the sum role's vector accesses
             (the layers _layer_adagrad and _wgrad_padded route away)."""
-        if self.separate_launches:
+        if step is not None and step.separate_launches:
             return False
         w_off, fi, fo, _ = self.layout[li]
         if fi > 384 or not self._wgrad_fits(li, g, acts):
             return False
         ptrs = [gflat.data_ptr()]
-        if self.fused_adagrad is not None:
-            ptrs += [self.flat.data_ptr(), self.fused_adagrad[0].data_ptr()]
+        if step is not None and step.adagrad is not None:
+            ptrs += [self.flat.data_ptr(), step.adagrad[0].data_ptr()]
         return all((p + 4 * w_off) % 16 == 0 for p in ptrs)
 
-    def _wgrad_job(self, li, acts, gflat, gout, g, gscale):
+    def _wgrad_job(self, li, acts, gflat, gout, g, gscale, *, step: Optional[TowerStep] = None):
         """Layer li's weight gradient (+ its fused Adagrad step) as a
         tt_mlp_wgrad_job; the partials alternate between two workspaces by
         layer parity (a job's partials are summed by the next launch)."""
         p = self._wgrad_problem(li, acts, gflat, gout, g, gscale)
         return hip_ops.mlp_wgrad_job(p["a"], p["g"], p["dwb"], gmask=p.get("gmask"), scale=p.get("scale"),
-                                     adagrad=self._layer_adagrad(li), tag=f"mlp_wgrad_l{li % 2}")
+                                     adagrad=self._layer_adagrad(li, step=step), tag=f"mlp_wgrad_l{li % 2}")
 
     def backward_split(self, acts: List[torch.Tensor], flat: torch.Tensor, gout: torch.Tensor,
-                       gscale: Optional[torch.Tensor], need_input_grad: bool):
+                       gscale: Optional[torch.Tensor], need_input_grad: bool, *,
+                       step: Optional[TowerStep] = None):
         """backward_acts in two phases: the input-gradient chain now (returns
         dx, None without need_input_grad) and the weight gradients when the
         returned finish() is called (returns the flat gradient) — the same
         kernels on the same operands as backward_acts, in IGRAD_FIRST order;
-        finish() applies the fused Adagrad step that was set at the split,
-        whenever it runs."""
+        finish() applies the Adagrad step of the TowerStep given at the
+        split, whenever it runs."""
         gs, g, dx = {}, gout, None
         for li in range(len(self.layout) - 1, -1, -1):
             gs[li] = g
@@ -381,40 +394,35 @@ class DenseStack:
             g = _rows(self._igrad_problem(li, acts, g, gscale))
             if li == 0:
                 dx = g
-        fused_adagrad = self.fused_adagrad
 
         def finish() -> torch.Tensor:
             gflat = torch.empty_like(flat)
-            prev, self.fused_adagrad = self.fused_adagrad, fused_adagrad
-            try:
-                for li in range(len(self.layout) - 1, -1, -1):
-                    self._wgrad_layer(li, acts, gflat, gout, gs[li], gscale)
-            finally:
-                self.fused_adagrad = prev
+            for li in range(len(self.layout) - 1, -1, -1):
+                self._wgrad_layer(li, acts, gflat, gout, gs[li], gscale, step=step)
             return gflat
 
         return dx, finish
 
-    def _layer_adagrad(self, li: int):
+    def _layer_adagrad(self, li: int, *, step: Optional[TowerStep] = None):
         """(param, accum, lr, eps) of layer li for its weight-gradient launches
-        to apply (marked in fused_applied), or None: no fused step, or the
+        to apply (marked in step.fused_layers), or None: no fused step, or the
         layer's region of the flat buffer is not 16-B aligned (a layer after
         one whose width is not a multiple of 4: the dense step applies it)."""
-        if self.fused_adagrad is None:
+        if step is None or step.adagrad is None:
             return None
-        acc, lr, eps = self.fused_adagrad
+        acc, lr, eps = step.adagrad
         w_off, fi, fo, _ = self.layout[li]
         n = (fi + 1) * fo
         param, accum = self.flat.data[w_off:w_off + n], acc[w_off:w_off + n]
         if param.data_ptr() % 16 or accum.data_ptr() % 16:
             return None
-        self.fused_applied.add(li)
+        step.fused_layers.add(li)
         return param, accum, lr, eps
 
-    def _wgrad_layer(self, li, acts, gflat, gout, g, gscale) -> None:
+    def _wgrad_layer(self, li, acts, gflat, gout, g, gscale, *, step: Optional[TowerStep] = None) -> None:
         if self._wgrad_fits(li, g, acts):
             p = self._wgrad_problem(li, acts, gflat, gout, g, gscale)
-            ad = self._layer_adagrad(li)
+            ad = self._layer_adagrad(li, step=step)
             if ad is not None:  # this layer's Adagrad step in the same launches
                 p["adagrad"] = ad
             _wgrad(p)
@@ -435,16 +443,13 @@ def pair_compatible(a: "DenseStack", b: "DenseStack") -> bool:
     return len(a.layout) == len(b.layout) and len(a.layout) > 0
 
 
-def forward_acts_pair(stacks, xs, flats) -> List[List[torch.Tensor]]:
+def forward_acts_pair(stacks, xs, flats, *, steps=None) -> List[List[torch.Tensor]]:
     """DenseStack.forward_acts of the two towers on ONE stream with every
     launch shared: one tt_mlp_pack_many for both towers' images (8 jobs at
-    one hidden layer), then one tt_mlp_rows_pair per layer."""
-    pre = [st.__dict__.get("_prepacked") == f.data_ptr() for st, f in zip(stacks, flats)]
+    one hidden layer; not those a TowerStep of `steps` says are packed), then
+    one tt_mlp_rows_pair per layer."""
     packed = [st._pack_jobs(f) for st, f in zip(stacks, flats)]
-    jobs = [j for p, (_, js) in zip(pre, packed) if not p for j in js]
-    for st, p in zip(stacks, pre):
-        if p:
-            st.__dict__["_prepacked"] = None
+    jobs = [j for ts, (_, js) in zip(steps or (None, None), packed) if ts is None or not ts.packed for j in js]
     for i in range(0, len(jobs), 8):
         hip_ops.mlp_pack_many(jobs[i:i + 8])
     acts = [[xs[0]], [xs[1]]]

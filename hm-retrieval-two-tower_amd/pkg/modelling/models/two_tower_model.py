@@ -16,9 +16,11 @@ can be captured once and replayed as a hipGraph (GraphedTrainStep).
 """
 from __future__ import annotations
 
+import functools
 import logging
 import os
-from typing import Any, Dict, Iterable, List, Optional
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -34,7 +36,7 @@ from pkg.modelling.models.abstract_keras_model import AbstractKerasModel, Tensor
 from pkg.modelling import hip_ops
 from pkg.modelling.layers.input_layer import InputLayer
 from pkg.modelling.models import tower as _tower_mod
-from pkg.modelling.models.tower import Tower
+from pkg.modelling.models.tower import Tower, TowerStep
 
 logger = logging.getLogger(__name__)
 
@@ -59,6 +61,22 @@ FUSED_DENSE_WGRAD = os.environ.get("TT_FUSED_DENSE_WGRAD", "1") == "1"
 # (tt_gather_multi_pack) instead of one pack launch per tower at the start of
 # each tower's forward (TT_PACK_WITH_GATHER=0).
 PACK_WITH_GATHER = os.environ.get("TT_PACK_WITH_GATHER", "1") == "1"
+
+
+@dataclass
+class TrainStep:
+    """The state of ONE train step: made by train_step, handed down as step=
+    (compute_loss, tower_loss, the towers-and-loss node and, per tower, the
+    DenseStacks), readable afterwards as model.last_step (its callbacks
+    dropped).  Nothing of it lives on the model or the stacks, so a step that
+    raises leaves nothing behind."""
+    mode: str = "plain"    # "plain" | "dense_early" | "fused": what the backward applies (train_step)
+    on_tower: Optional[Callable] = None   # on_tower(i, input_grad, flat_grad): tower i's gradients exist
+    on_dx: Optional[Callable] = None      # on_dx(i, dx): tower i's input gradient exists (IGRAD_FIRST, fused)
+    dense_done: set = field(default_factory=set)    # towers whose dense update the backward applied
+    sparse_done: set = field(default_factory=set)   # towers whose embedding update ran at their input gradient
+    ids_ready: Optional[torch.cuda.Event] = None    # recorded after the gather: the id sorts wait for it only
+    towers: Tuple[TowerStep, TowerStep] = field(default_factory=lambda: (TowerStep(), TowerStep()))
 
 
 class TwoTowerModel(AbstractKerasModel):
@@ -197,6 +215,7 @@ class TwoTowerModel(AbstractKerasModel):
         self.logq_correction = LogQCorrection(candidate_prob_lookup) if candidate_prob_lookup else None
         self._logq_rows: Optional[torch.Tensor] = None
         self.optimizer = None
+        self.last_step: Optional[TrainStep] = None  # the last train_step's state, for inspection
         self.loss = InBatchSoftmaxCrossEntropy()
         self.initialise_model()
 
@@ -338,7 +357,31 @@ class TwoTowerModel(AbstractKerasModel):
             self._mixed_logq[key] = torch.as_tensor(table, device=self.device)
         return self._mixed_logq[key]
 
-    def _compute_loss_mixed(self, x: Dict[str, Any]) -> torch.Tensor:
+    def _gathered(self, step: TrainStep, pack: list, qi: torch.Tensor) -> None:
+        """After a training step's gather launches: the towers' images are
+        this step's where they rode along (pack), and the ids are ready."""
+        for ts in step.towers:
+            ts.packed = bool(pack)
+        if qi.is_cuda:
+            # the embedding update's id sort needs only these ids
+            step.ids_ready = torch.cuda.Event()
+            step.ids_ready.record()
+            if step.mode == "fused":
+                # fused apply (train_step): the per-tower id sorts captured
+                # right after the gather (their only input), so they overlap
+                # the forward instead of landing in front of the backward
+                self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
+
+    def _gather_pack_jobs(self) -> list:
+        """Both towers' MLP weight-image jobs for a training step's gather
+        launch (PACK_WITH_GATHER), or none: more than 8 do not fit it, and
+        each tower's forward then packs its own."""
+        if not (PACK_WITH_GATHER and self.device.type == "cuda"):
+            return []
+        pack = [j for t in self.towers for j in t.dense.prepack_jobs(t.dense.flat.detach())]
+        return pack if len(pack) <= 8 else []
+
+    def _compute_loss_mixed(self, x: Dict[str, Any], step: TrainStep) -> torch.Tensor:
         """The training loss with num_sampled_negatives: the candidate side
         sampled and assembled by one tt_mixed_candidates launch into a
         persistent [F, B + M] buffer (so a captured step replays it), each
@@ -377,65 +420,48 @@ class TwoTowerModel(AbstractKerasModel):
             if self.logq_correction is not None:
                 out = torch.empty(B + M, 1, dtype=torch.float32, device=self.device)
                 call = ([(self.mixture_logq_table(B).view(-1, 1), ids_all, 0)], out)
-            pack = []
-            if PACK_WITH_GATHER and self.device.type == "cuda":
-                pack = [j for t in self.towers for j in t.dense.prepack_jobs(t.dense.flat.detach())]
-                if len(pack) > 8:
-                    for t in self.towers:
-                        t.dense.__dict__["_prepacked"] = None
-                    pack = []
+            pack = self._gather_pack_jobs()
             (qi,) = InputLayer.gather_many([self.query_tower.input_layer], [q], pack_jobs=pack or None)
             (ci,) = InputLayer.gather_many([layer], [cm], extra=[call] if call is not None else ())
-            if qi.is_cuda:
-                self._ids_ready = torch.cuda.Event()
-                self._ids_ready.record()
-                if getattr(self, "_on_tower", None) == self._apply_tower:
-                    self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
+            self._gathered(step, pack, qi)
             logq = call[1].view(-1) if call is not None else None
             return self.tower_loss(qi, ci, logq, ids_all if self.remove_accidental_hits else None,
-                                   self.sample_weights(x))
+                                   self.sample_weights(x), step=step)
 
-    def compute_loss(self, x: Dict[str, Any], training: bool = True) -> torch.Tensor:
+    def compute_loss(self, x: Dict[str, Any], training: bool = True, *, step: Optional[TrainStep] = None
+                     ) -> torch.Tensor:
+        """The batch's loss.  step: train_step's TrainStep; a training loss
+        without one is a plain step's (nothing applied inside its backward)."""
+        if training and step is None:
+            step = TrainStep()
         if training and self.num_sampled_negatives is not None:
-            return self._compute_loss_mixed(x)
+            return self._compute_loss_mixed(x, step)
         q, c = self._split(x)
         with torch.set_grad_enabled(training):
             call = self._logq_call(x)  # rides in the towers' gather launch
             # ... and so do the towers' MLP weight images of this forward (at most 8 jobs)
-            pack = []
-            if training and PACK_WITH_GATHER and torch.is_grad_enabled() and self.device.type == "cuda":
-                pack = [j for t in self.towers for j in t.dense.prepack_jobs(t.dense.flat.detach())]
-                if len(pack) > 8:
-                    for t in self.towers:
-                        t.dense.__dict__["_prepacked"] = None
-                    pack = []
+            pack = self._gather_pack_jobs() if training else []
             qi, ci = InputLayer.gather_many([self.query_tower.input_layer, self.candidate_tower.input_layer], [q, c],
                                             extra=[call] if call is not None else (), pack_jobs=pack or None)
-            if training and qi.is_cuda:
-                # the embedding update's id sort needs only these ids
-                self._ids_ready = torch.cuda.Event()
-                self._ids_ready.record()
-                if getattr(self, "_on_tower", None) == self._apply_tower:
-                    # fused apply (train_step): the per-tower id sorts captured
-                    # right after the gather (their only input), so they overlap
-                    # the forward instead of landing in front of the backward
-                    self.optimizer.prepare_towers(self.towers, ["", TOWER_C_SCOPE])
+            if training:
+                self._gathered(step, pack, qi)
             logq = call[1].view(-1) if call is not None else self.candidate_logq(x)
-            return self.tower_loss(qi, ci, logq, self.candidate_ids(x), self.sample_weights(x))
+            return self.tower_loss(qi, ci, logq, self.candidate_ids(x), self.sample_weights(x), step=step)
 
     def tower_loss(self, qi: torch.Tensor, ci: torch.Tensor, logq: Optional[torch.Tensor],
-                   ids: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   ids: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, *,
+                   step: Optional[TrainStep] = None) -> torch.Tensor:
         """Loss from the gathered tower inputs: with gradients, both MLPs and the
         in-batch loss run as one autograd node (losses.towers_inbatch_softmax_xent).
         ids: candidate_ids(x) (accidental hits removed), or None.  weights:
-        sample_weights(x), or None (an unweighted batch: the calls as ever)."""
+        sample_weights(x), or None (an unweighted batch: the calls as ever).
+        step: the TrainStep this loss belongs to (compute_loss), or None."""
         wkw = {} if weights is None else {"weights": weights, "weight_scale": float(self.sample_weight_scale)}
         if self.num_hard_negatives is not None:  # hard-negative mining, on every path through here
             wkw["num_hard_negatives"] = self.num_hard_negatives
         if torch.is_grad_enabled():
             return towers_inbatch_softmax_xent(qi, ci, self.query_tower.dense, self.candidate_tower.dense, logq,
-                                               self.loss.reduction, getattr(self, "_on_tower", None),
-                                               getattr(self, "_on_dx", None), ids, **wkw)
+                                               self.loss.reduction, ids=ids, step=step, **wkw)
         sq, sc = self.query_tower.dense, self.candidate_tower.dense
         if sq.normalize or sc.normalize:  # both outputs normalised in one launch, after both towers
             q, c, _ = normalized_outputs(sq, sc, sq.forward_acts(qi, sq.flat.detach())[-1],
@@ -490,40 +516,33 @@ class TwoTowerModel(AbstractKerasModel):
         fused = self.fused_optimizer_apply and isinstance(self.optimizer, Adagrad) and self.device.type == "cuda"
         dense_early = (not fused and not clips and DENSE_EARLY and isinstance(self.optimizer, Adagrad)
                        and self.device.type == "cuda")
-        self._dense_done = set()
-        self._sparse_done = set()
-        for t in self.towers:
-            t.dense.fused_applied = set()
-            t.dense.fused_adagrad = None
-            t.dense.separate_launches = bool(fused)
+        step = self.last_step = TrainStep("fused" if fused else "dense_early" if dense_early else "plain")
+        for t, ts in zip(self.towers, step.towers):
+            ts.separate_launches = bool(fused)
             if dense_early and FUSED_DENSE_WGRAD:
                 opt = self.optimizer
                 (acc,) = opt._slot(t.dense.flat, 1, opt.initial_accumulator_value)
-                t.dense.fused_adagrad = (acc, opt.learning_rate, opt.epsilon)
-        self._on_tower = self._apply_tower if fused else (self._apply_dense_tower if dense_early else None)
-        # fused: each tower's embedding update the moment its input gradient
-        # exists (the weight gradients follow it on that tower's stream)
-        self._on_dx = self._apply_tower_sparse if (fused and _tower_mod.IGRAD_FIRST) else None
-        try:
-            loss = self.compute_loss(data, training=True)  # fused: issues the per-tower id sorts
-        finally:
-            self._on_tower = None
-            self._on_dx = None
+                ts.adagrad = (acc, opt.learning_rate, opt.epsilon)
+        if fused:
+            step.on_tower = functools.partial(self._apply_tower, step)
+            # each tower's embedding update the moment its input gradient
+            # exists (the weight gradients follow it on that tower's stream)
+            step.on_dx = functools.partial(self._apply_tower_sparse, step) if _tower_mod.IGRAD_FIRST else None
+        elif dense_early:
+            step.on_tower = functools.partial(self._apply_dense_tower, step)
+        loss = self.compute_loss(data, training=True, step=step)  # fused: issues the per-tower id sorts
         fwd_done = None
         if not fused and hasattr(self.optimizer, "prepare") and loss.is_cuda:
             # the id sort waits for the gather only (compute_loss recorded the
             # event), not the whole forward: 6.6 us/step on the C3 step over 6
             # interleaved pairs
-            fwd_done = self._ids_ready
+            fwd_done = step.ids_ready
         for t in self.towers:
             t.dense.flat.grad = None
         if getattr(self, "_one", None) is None or self._one.device != loss.device:
             self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
-        try:
-            loss.backward(self._one)  # a persistent seed: no ones-fill launch per step
-        finally:
-            for t in self.towers:
-                t.dense.fused_adagrad = None
+        loss.backward(self._one)  # a persistent seed: no ones-fill launch per step
+        step.on_tower = step.on_dx = None  # what stays as last_step is plain data, with no way back to the model
         if fused:
             self.optimizer.iterations += 1
             # the update is applied: a later apply_gradients must not apply it again
@@ -531,9 +550,8 @@ class TwoTowerModel(AbstractKerasModel):
                 t.dense.flat.grad = None
                 t.input_layer.last_grad = None
         else:
-            for i in self._dense_done:  # applied inside the backward: not again
+            for i in step.dense_done:  # applied inside the backward: not again
                 self.towers[i].dense.flat.grad = None
-            self._dense_done = set()
             if fwd_done is not None:
                 # the embedding update's id sort needs only the forward's ids; issued
                 # after the backward (so the backward's chains are launched first)
@@ -542,21 +560,24 @@ class TwoTowerModel(AbstractKerasModel):
             self.optimizer.apply_gradients(self.towers)
         return {"loss": loss.detach()}
 
-    def _apply_tower(self, i: int, input_grad: Optional[torch.Tensor], flat_grad: torch.Tensor) -> None:
-        if i in self._sparse_done:  # its embedding update ran at the input gradient
+    # the step's callbacks (train_step binds the TrainStep: on_tower(i, ...), on_dx(i, dx))
+    def _apply_tower(self, step: TrainStep, i: int, input_grad: Optional[torch.Tensor],
+                     flat_grad: torch.Tensor) -> None:
+        if i in step.sparse_done:  # its embedding update ran at the input gradient
             self.optimizer.apply_dense(self.towers[i], flat_grad)
             return
         self.optimizer.apply_tower(self.towers[i], input_grad, flat_grad)
 
-    def _apply_tower_sparse(self, i: int, input_grad: Optional[torch.Tensor]) -> None:
+    def _apply_tower_sparse(self, step: TrainStep, i: int, input_grad: Optional[torch.Tensor]) -> None:
         self.optimizer.apply_tower_sparse(self.towers[i], input_grad)
-        self._sparse_done.add(i)
+        step.sparse_done.add(i)
 
-    def _apply_dense_tower(self, i: int, input_grad: Optional[torch.Tensor], flat_grad: torch.Tensor) -> None:
-        st = self.towers[i].dense
-        if st.fused_applied:  # the weight-gradient launches applied those layers' step
+    def _apply_dense_tower(self, step: TrainStep, i: int, input_grad: Optional[torch.Tensor],
+                           flat_grad: torch.Tensor) -> None:
+        st, applied = self.towers[i].dense, step.towers[i].fused_layers
+        if applied:  # the weight-gradient launches applied those layers' step
             for li, (w_off, fi, fo, _) in enumerate(st.layout):
-                if li not in st.fused_applied:  # a layer outside tt_mlp_wgrad's contract
+                if li not in applied:  # a layer outside tt_mlp_wgrad's contract
                     n = (fi + 1) * fo
                     (acc,) = self.optimizer._slot(st.flat, 1, self.optimizer.initial_accumulator_value)
                     hip_ops.dense_adagrad(st.flat.data[w_off:w_off + n], acc[w_off:w_off + n],
@@ -564,7 +585,7 @@ class TwoTowerModel(AbstractKerasModel):
                                           self.optimizer.epsilon)
         else:
             self.optimizer.apply_dense(self.towers[i], flat_grad)
-        self._dense_done.add(i)
+        step.dense_done.add(i)
 
     def fit(self, dataset: Iterable[Dict[str, Any]], epochs: int = 1, callbacks=None,
             use_graph: bool = False) -> Dict[str, List[float]]:

@@ -87,10 +87,7 @@ def _assert_same_state(a, b, what):
 def _backward_only(m, x):
     """The step's forward and backward with no update from inside the
     backward (the path a clipping optimizer takes), nothing applied."""
-    m._on_tower = m._on_dx = None
     for t in m.towers:
-        t.dense.fused_applied = set()
-        t.dense.fused_adagrad = None
         t.dense.flat.grad = None
     loss = m.compute_loss(x, training=True)
     loss.backward()

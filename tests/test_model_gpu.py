@@ -241,7 +241,7 @@ def test_fused_optimizer_apply_bit_identical_to_unfused(cuda):
 
 @pytest.mark.parametrize("fused", [False, True])
 def test_igrad_first_order_bit_identical(cuda, monkeypatch, fused):
-    """TT_IGRAD_FIRST (the default): each tower's input-gradient chain before
+    """TT_IGRAD_FIRST (off by default): each tower's input-gradient chain before
     its weight gradients, and in the fused step the embedding update issued at
     the input gradient, ahead of the weight gradients on that tower's stream —
     the same kernels on the same operands, so losses, tables, accumulators and
@@ -281,7 +281,10 @@ def test_dense_early_bit_identical_to_dense_after_join(cuda, monkeypatch):
         la = a.train_step(x)["loss"]
         monkeypatch.setattr(ttm, "DENSE_EARLY", True)
         lb = b.train_step(x)["loss"]
-        assert b._dense_done == set() and all(t.dense.flat.grad is None for t in b.towers)
+        # both towers' dense updates were applied inside the backward, and nothing is left to re-apply
+        assert b.last_step.mode == "dense_early" and b.last_step.dense_done == {0, 1}
+        assert a.last_step.mode == "plain" and a.last_step.dense_done == set()
+        assert all(t.dense.flat.grad is None for t in b.towers)
         assert torch.equal(la, lb), (i, B)
         sa, sb = _state(a), _state(b)
         for k in sa:
@@ -333,7 +336,7 @@ def test_fused_dense_wgrad_bit_identical(cuda, monkeypatch, pair):
         la = a.train_step(x)["loss"]
         monkeypatch.setattr(ttm, "FUSED_DENSE_WGRAD", True)
         lb = b.train_step(x)["loss"]
-        assert all(bool(t.dense.fused_applied) == (pair == 0) for t in b.towers)
+        assert all(bool(ts.fused_layers) == (pair == 0) for ts in b.last_step.towers)
         assert torch.equal(la, lb), (i, B)
         sa, sb = _state(a), _state(b)
         for k in sa:
@@ -360,7 +363,8 @@ def test_pack_with_gather_bit_identical(cuda, monkeypatch, pair):
         la = a.train_step(x)["loss"]
         monkeypatch.setattr(ttm, "PACK_WITH_GATHER", True)
         lb = b.train_step(x)["loss"]
-        assert all(t.dense.__dict__.get("_prepacked") is None for t in b.towers)  # consumed by the forward
+        # packed by the gather launch with the flag on, by each tower's forward with it off
+        assert all(ts.packed for ts in b.last_step.towers) and not any(ts.packed for ts in a.last_step.towers)
         assert torch.equal(la, lb), (i, B)
         sa, sb = _state(a), _state(b)
         for k in sa:
@@ -398,7 +402,7 @@ def test_fused_dense_wgrad_odd_hidden_width_bit_identical(cuda, monkeypatch):
         lb = b.train_step(x)["loss"]
         # layer 0 applied by its weight-gradient launch; layer 1 (width 66, padded path) and
         # layer 2 (its region 8-B aligned) by the dense step
-        assert all(t.dense.fused_applied == {0} for t in b.towers)
+        assert all(ts.fused_layers == {0} for ts in b.last_step.towers)
         assert torch.equal(la, lb), (i, B)
         sa, sb = _state(a), _state(b)
         for k in sa:
@@ -424,14 +428,14 @@ def test_gather_multi_pack_equals_two_launches(cuda):
     flat = st.flat.detach()
     jobs = st.prepack_jobs(flat)
     hip_ops.gather_multi([([(num, None, 0), (tab, ids, 1)], outs[0])], B, pack_jobs=jobs)
-    imgs1 = {k: v.clone() for k, v in st.__dict__["_images"].items()}
-    for v in st.__dict__["_images"].values():
+    imgs1 = {k: v.clone() for k, v in st.images.items()}
+    for v in st.images.values():
         v.zero_()
     hip_ops.gather_multi([([(num, None, 0), (tab, ids, 1)], outs[1])], B)
     hip_ops.mlp_pack_many(jobs)
     torch.cuda.synchronize()
     assert torch.equal(outs[0], outs[1])
-    for k, v in st.__dict__["_images"].items():
+    for k, v in st.images.items():
         assert torch.equal(v, imgs1[k]), k
 
 
